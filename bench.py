@@ -57,7 +57,59 @@ def parse():
     ap.add_argument("--no-parity", action="store_true", help="skip the headline parity sample against the oracle")
     ap.add_argument("--sustained-steps", type=int, default=150,
                     help="N = 1: steps of the extra steady-state measurement taken AFTER the contract's timed region (0 = off)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         f"at most {DUMP_MAX_BYTES >> 20} MB in all; the thresholded frames as a fixed seeded sample of whole "
+                         "frames); rank 0 writes the gathered records and its own shard's arrays")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_FRAMES_BYTES = 32 << 20     # share of the cap the frame sample may take; the per-frame outputs use the rest
+
+
+def _row_sample(rows, row_bytes, budget, seed):
+    """sorted row indices of a fixed seeded sample that fits `budget` bytes (every row when they all fit)"""
+    import numpy as np
+
+    k = max(1, min(rows, budget // max(row_bytes, 1)))
+    if k == rows:
+        return np.arange(rows)
+    return np.sort(np.random.default_rng(seed).choice(rows, size=k, replace=False))
+
+
+def dump_outputs(out_dir, res, record):
+    """Writes the timed path's results (pipeline.EpidResult + the record table the step returned) as float32 / float64 .npy
+    files: record, threshold, fwxm, status and profile whole unless they alone pass the cap, frames as a seeded sample of
+    whole frames with their indices in frames_index.npy.  Returns {name: shape}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n, h, w = res.frames.shape
+    per_frame = {"record": record.to("cpu").numpy().astype(np.float64),
+                 "threshold": res.threshold.to("cpu").numpy().astype(np.float64),
+                 "fwxm": res.fwxm.to("cpu").numpy().astype(np.float64),
+                 "status": res.status.to("cpu").numpy().astype(np.float64),
+                 "profile": res.profile.to("cpu").numpy().astype(np.float64)}
+    arrays = {}
+    rest = DUMP_MAX_BYTES - DUMP_FRAMES_BYTES
+    for name, a in per_frame.items():
+        idx = _row_sample(a.shape[0], a[:1].nbytes + 8, rest // len(per_frame), seed=1)
+        arrays[name] = a[idx]
+        if len(idx) < a.shape[0]:
+            arrays[f"{name}_index"] = idx.astype(np.float64)
+    idx = _row_sample(n, h * w * 4 + 8, DUMP_FRAMES_BYTES, seed=0)
+    # (uint16 rows one by one: torch has no indexed gather for uint16; float32 holds every uint16 exactly)
+    arrays["frames"] = np.stack([res.frames[int(i)].to("cpu").numpy() for i in idx]).astype(np.float32)
+    arrays["frames_index"] = idx.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def mfma_view(tiles, seconds):
@@ -423,15 +475,17 @@ def main():
     pipe = EpidPipeline(n, h, w, dev)
 
     pending = []          # work handles of the record gathers in flight (N > 1): the gather of step k overlaps step k + 1
+    last = {}             # the latest step's result and record table (--dump-outputs)
 
     def step(events=None):
         res = pipe.run(frames, events)
         rec = res.record()
-        if dist is None:
-            return rec
-        while len(pending) >= 2:          # at most two gathers in flight: their output buffers stay bounded
-            pending.pop(0).wait()
-        return pdist.all_gather_records(rec, n_total, pending)
+        if dist is not None:
+            while len(pending) >= 2:      # at most two gathers in flight: their output buffers stay bounded
+                pending.pop(0).wait()
+            rec = pdist.all_gather_records(rec, n_total, pending)
+        last["res"], last["rec"] = res, rec
+        return rec
 
     def drain():
         while pending:
@@ -476,6 +530,9 @@ def main():
             traffic, traffic_src = tj.get(dominant), tj.get("_measured_at")
         except Exception:
             traffic = None
+
+    # the last timed step's outputs, before the sustained / parity passes below reuse the pipeline's buffers
+    dumped = dump_outputs(args.dump_outputs, last["res"], last["rec"]) if args.dump_outputs and rank == 0 else None
 
     if rank == 0:
         total_frames = n_total * args.steps
@@ -530,6 +587,8 @@ def main():
                 "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
             },
         }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if world == 1 and args.sustained_steps > 0:
             # The contract's W + K steps last ~25 ms: inside the power governor's ramp (an MI355X reaches its 1400 W cap under
             # gauss2d_mm; after an idle period the first launches run at boost clocks, the next ~10 are throttled hard, and the
