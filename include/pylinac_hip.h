@@ -730,8 +730,9 @@ int pl_pf_windows(const uint16_t* in, int64_t n, int h, int w, const double* d_s
                   const double* d_spacing, const int32_t* d_leaf_top, const int32_t* d_leaf_bottom, int nleaves,
                   double height_threshold, double edge_threshold, int lmax, double* d_prof, int32_t* d_len,
                   double* d_offset, int32_t* d_status, void* stream);
-/* pl_pf_windows with the caller's bound on the window height (max_rows = the tallest bottom - top of the leaf table, 1..48):
- * the kernel's LDS per wave follows it, which is what decides how many waves hide each other's latency. */
+/* pl_pf_windows with the caller's bound on the window height (max_rows = the tallest bottom - top of the leaf table, 1..64):
+ * the kernel's LDS per wave follows it, which is what decides how many waves hide each other's latency.  pl_pf_windows itself
+ * takes windows of at most 48 rows; windows taller than the bound, or wider than 128 columns, get status 3. */
 int pl_pf_windows_rows(const uint16_t* in, int64_t n, int h, int w, const double* d_sub, const double* d_div,
                        const int32_t* d_pk_count, const int32_t* d_pk_idx, const double* d_pk_val, int cap,
                        const double* d_spacing, const int32_t* d_leaf_top, const int32_t* d_leaf_bottom, int nleaves,
@@ -748,7 +749,8 @@ int pl_pf_positions(const int32_t* d_status, const double* d_fwxm, const double*
  * rows; np.std over axis 0 and np.median over axis 1 of the window, i.e. the transposed computation with numpy's summation
  * order for a non-contiguous axis).  fwxm_params: pl_find_peaks parameters of FWXMProfile.field_edge_idx (fwxm_height,
  * max_number = 1).  d_prof (optional, float64 [n*nleaves*cap][lmax >= 128]) receives the window profiles.  max_rows: the
- * widest leaf in pixels, 1..48 (10 mm leaves on the finest supported EPID at isocentre scale are 45 pixels).
+ * widest leaf in pixels, 1..64 (10 mm leaves on the finest supported EPID at isocentre scale are 45 pixels, on a 150 dpi film
+ * scan 59); windows taller than max_rows or wider than 128 columns get status 3.
  * exact_deviation: 0 = the edge test max(std) < edge_threshold * median(std) (:855) is decided from exact integer row moments
  * whenever it holds or fails by more than numpy's rounding could move it (1e-7 relative), and numpy's float64 sequence only
  * runs for a window inside that margin; 1 = always evaluate numpy's sequence.  Same results either way. */
@@ -757,6 +759,20 @@ int pl_pf_measure(const uint16_t* in, int64_t n, int h, int w, int orientation, 
                   const int32_t* d_leaf_lo, const int32_t* d_leaf_hi, int nleaves, int max_rows, double height_threshold,
                   double edge_threshold, int exact_deviation, const pl_peak_params* fwxm_params, double* d_rec, int32_t* d_status,
                   double* d_prof, int lmax, void* stream);
+/* Float64 frames (a rescaled DICOM series with a fractional slope or intercept), q = (a - sub_i) / div_i by true float64
+ * division: pl_scaled_colmean_f64 = pl_scaled_colmean, pl_scaled_rowmean_f64 = pl_scaled_rowmean (rows of at most 4096
+ * pixels), pl_pf_measure_f64 = pl_pf_measure with exact_deviation = 1 (numpy's float64 np.std for every window).  Every
+ * pixel must be finite: a window holding a NaN or an infinity gets status 3 (the caller refuses the whole frame). */
+int pl_scaled_colmean_f64(const double* in, int64_t n, int h, int w, const double* d_sub, const double* d_div, double* d_out,
+                          void* stream);
+int pl_scaled_rowmean_f64(const double* in, int64_t n, int h, int w, const double* d_sub, const double* d_div,
+                          const int32_t* d_leaf_start, const int32_t* d_leaf_len, int nleaves, const int32_t* d_program, int nprog,
+                          double* d_out, void* stream);
+int pl_pf_measure_f64(const double* in, int64_t n, int h, int w, int orientation, const double* d_sub, const double* d_div,
+                      const int32_t* d_pk_count, const int32_t* d_pk_idx, const double* d_pk_val, int cap, const double* d_spacing,
+                      const int32_t* d_leaf_lo, const int32_t* d_leaf_hi, int nleaves, int max_rows, double height_threshold,
+                      double edge_threshold, const pl_peak_params* fwxm_params, double* d_rec, int32_t* d_status,
+                      double* d_prof, int lmax, void* stream);
 /* np.mean(q, 1) -> d_out float64 [n][h] (the leaf profile of LEFT_RIGHT pickets, picketfence.py:749) in numpy's PAIRWISE
  * summation order for the contiguous axis.  The summation tree of a row of w values is laid out by the caller
  * (ops.pairwise_plan): d_leaf_start / d_leaf_len int32 [nleaves] = the leaf blocks (<= 128 values each), d_program int32

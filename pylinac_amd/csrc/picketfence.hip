@@ -17,6 +17,13 @@
 //                       normalization=MAX), :1609-1614)
 //   pl_pf_positions     centre + max(approx_idx - spacing/2, 0)    picketfence.py:1624-1627
 // One wave per window; the window's integer pixels are staged in LDS once.
+//
+// The *_f64 entry points take float64 frames instead (a rescaled DICOM series with a fractional slope: what the reference's
+// apply_rescale hands PicketFence.__init__).  Same sequence, the pixels are doubles: q divides truly (the reciprocal-plus-FMA
+// quotient of pl_quot_make is exact for integer pixels only), the edge test always evaluates numpy's float64 np.std, and the
+// window is staged as q (one division per pixel; np.max and the column medians select among those values directly).
+#include <type_traits>
+
 #include "pl_common.h"
 #include "peaks_device.h"
 
@@ -26,8 +33,12 @@ namespace {
 #define PL_PF_VARIANT 0         // 1 / 2 / 3: stopwatch builds that skip a stage of pf_windows_kernel (WRONG results; scripts/)
 #endif
 constexpr int kThreads = 256;
-constexpr int kMaxRows = 48;    // window rows  (leaf width in pixels)
+constexpr int kMaxRows = 48;    // window rows (leaf width in pixels) of the launch configuration every EPID leaf fits
+constexpr int kMaxRowsTall = 64;  // window rows of the tall-leaf instantiations (film scans, fine panels): one lane per row
 constexpr int kMaxCols = 128;   // window cols  (picket spacing in pixels); numpy pairwise-sum single block
+
+// q = (a - s) / d by true float64 division: the pixels of the float64 path are not integers
+__device__ __forceinline__ PlQuot pl_quot_div(double s, double d) { return PlQuot{s, d, 0.0, false}; }
 
 __global__ void __launch_bounds__(kThreads)
 scaled_colmean_kernel(const unsigned short* __restrict__ in, int h, int w, int col_tiles,
@@ -104,30 +115,84 @@ scaled_colmeanv_kernel(const unsigned short* __restrict__ in, int h, int w, int6
   for (int j = 0; j < COLS; ++j) o[j] = a[j] / (double)h;
 }
 
+// np.mean(q, 0) of a float64 frame: a lane owns COLS adjacent columns (COLS = 2: one 16-byte load per row) and keeps U rows
+// of loads in flight; each column is still summed row by row like numpy's, with q's true division per pixel
+template <int COLS, int U>
+__global__ void __launch_bounds__(kThreads)
+scaled_colmean_f64_kernel(const double* __restrict__ in, int h, int w, int64_t total_groups, const double* __restrict__ sub,
+                          const double* __restrict__ div, double* __restrict__ out) {
+  static_assert(COLS == 1 || COLS == 2, "one or two columns per lane");
+  const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (g >= total_groups) return;
+  const int gpr = w / COLS;
+  const size_t frame = (size_t)(g / gpr);
+  const int c = (int)(g % gpr) * COLS;
+  const double* p = in + frame * (size_t)h * w + c;
+  const PlQuot k = pl_quot_div(sub[frame], div[frame]);
+  double a[COLS];
+#pragma unroll
+  for (int j = 0; j < COLS; ++j) a[j] = 0.0;
+  struct Px { double v[COLS]; };
+  auto load = [&](int r) {
+    Px x;
+    if constexpr (COLS == 2) {
+      const double2 q = *reinterpret_cast<const double2*>(p + (size_t)r * w);
+      x.v[0] = q.x; x.v[1] = q.y;
+    } else {
+      x.v[0] = p[(size_t)r * w];
+    }
+    return x;
+  };
+  auto add = [&](const Px& x) {
+#pragma unroll
+    for (int j = 0; j < COLS; ++j) a[j] = a[j] + pl_quot(k, x.v[j]);
+  };
+  int r = 0;
+  for (; r + U <= h; r += U) {
+    Px x[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) x[u] = load(r + u);
+#pragma unroll
+    for (int u = 0; u < U; ++u) add(x[u]);
+  }
+  for (; r < h; ++r) add(load(r));
+  double* o = out + frame * (size_t)w + c;
+#pragma unroll
+  for (int j = 0; j < COLS; ++j) o[j] = a[j] / (double)h;
+}
+
 // np.mean(image, 1) of the normalised frame (LEFT_RIGHT pickets, picketfence.py:749): along the CONTIGUOUS axis numpy sums
 // pairwise (numpy/_core/src/umath/loops_utils.h.src): a row of more than 128 values is halved recursively (first half rounded
 // down to a multiple of 8) into leaf blocks of at most 128, each summed with eight running partial sums combined as a tree,
 // and the leaves are added up along the recursion tree.  The tree depends on the row length only, so the HOST lays it out
 // once (leaf starts / lengths and a postfix program: k >= 0 pushes leaf k's sum, -1 adds the two on top); a wave stages its
-// row in LDS, eight lanes sum each leaf (lane j = partial sum j), one lane runs the program.
+// row in LDS, eight lanes sum each leaf (lane j = partial sum j), one lane runs the program.  T = double: the float64 frames'
+// form (true division, see pl_quot_div).
 constexpr int kRmMaxLeaves = 256;
 
+template <typename T>
+__device__ __forceinline__ PlQuot pf_quot(double s, double d) {
+  if constexpr (std::is_same<T, double>::value) return pl_quot_div(s, d);
+  else return pl_quot_make(s, d);
+}
+
+template <typename T>
 __global__ void __launch_bounds__(kThreads)
-scaled_rowmean_kernel(const unsigned short* __restrict__ in, int h, int w, int64_t total_rows, const double* __restrict__ sub,
+scaled_rowmean_kernel(const T* __restrict__ in, int h, int w, int64_t total_rows, const double* __restrict__ sub,
                       const double* __restrict__ div, const int32_t* __restrict__ leaf_start, const int32_t* __restrict__ leaf_len,
                       int nleaves, const int32_t* __restrict__ program, int nprog, double* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char rm_lds[];
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t row = (int64_t)blockIdx.x * (kThreads / PL_WAVE) + wv;
   if (row >= total_rows) return;
-  const size_t wave_bytes = (((size_t)w * 2 + 15) & ~(size_t)15) + (size_t)(kRmMaxLeaves + 16) * sizeof(double);
-  unsigned short* srow = reinterpret_cast<unsigned short*>(rm_lds + (size_t)wv * wave_bytes);
-  double* ssum = reinterpret_cast<double*>(rm_lds + (size_t)wv * wave_bytes + (((size_t)w * 2 + 15) & ~(size_t)15));
+  const size_t wave_bytes = (((size_t)w * sizeof(T) + 15) & ~(size_t)15) + (size_t)(kRmMaxLeaves + 16) * sizeof(double);
+  T* srow = reinterpret_cast<T*>(rm_lds + (size_t)wv * wave_bytes);
+  double* ssum = reinterpret_cast<double*>(rm_lds + (size_t)wv * wave_bytes + (((size_t)w * sizeof(T) + 15) & ~(size_t)15));
   const int64_t frame = row / h;
-  const unsigned short* p = in + row * (int64_t)w;
+  const T* p = in + row * (int64_t)w;
   for (int c = lane; c < w; c += PL_WAVE) srow[c] = p[c];
   pl_wave_sync();
-  const PlQuot k = pl_quot_make(sub[frame], div[frame]);
+  const PlQuot k = pf_quot<T>(sub[frame], div[frame]);
   auto at = [&](int c) { return pl_quot(k, (double)srow[c]); };
   const int j = lane & 7, g = lane >> 3;
   for (int k0 = 0; k0 < nleaves; k0 += 8) {                  // wave-uniform trip count
@@ -217,18 +282,23 @@ __device__ __forceinline__ double pairwise_sum_block(int n, F at) {
 }
 
 // Middle order statistics of a window column (n <= N rows, pitch `pitch` in LDS) by Batcher's odd-even merge sort on N
-// registers: lo = sorted[N/2 - 1], hi = sorted[N/2] of the column padded with floor((N - n) / 2) values of -1 in front and
-// INT_MAX behind.  For even n these are the two middle values, for odd n `lo` is THE median.
-template <int N>
-__device__ __forceinline__ void pf_column_median(const unsigned short* col, int pitch, int n, int& lo, int& hi) {
-  int v[N];
+// registers: lo = sorted[N/2 - 1], hi = sorted[N/2] of the column padded with floor((N - n) / 2) values below every pixel in
+// front and values above every pixel behind (-1 / INT_MAX for uint16 pixels, -inf / +inf for finite doubles).  For even n
+// these are the two middle values, for odd n `lo` is THE median.
+template <int N, typename T, typename K>
+__device__ __forceinline__ void pf_column_median(const T* col, int pitch, int n, K& lo, K& hi) {
+  constexpr bool kF64 = std::is_same<T, double>::value;
+  K below, above;
+  if constexpr (kF64) { below = -__builtin_huge_val(); above = __builtin_huge_val(); }
+  else { below = -1; above = 0x7fffffff; }
+  K v[N];
   const int pad_lo = (N - n) >> 1;
 #pragma unroll
   for (int a = 0; a < N; ++a) {
     const int r = a - pad_lo;                        // wave-uniform; the read itself is unconditional (clamped row)
     const int rc = r < 0 ? 0 : (r < n ? r : n - 1);
-    const int x = (int)col[rc * pitch];
-    v[a] = r < 0 ? -1 : (r < n ? x : 0x7fffffff);
+    const K x = (K)col[rc * pitch];
+    v[a] = r < 0 ? below : (r < n ? x : above);
   }
 #pragma unroll
   for (int p = 1; p < N; p <<= 1)
@@ -239,7 +309,7 @@ __device__ __forceinline__ void pf_column_median(const unsigned short* col, int 
 #pragma unroll
         for (int i = 0; i < k; ++i)
           if (i + j + k < N && (i + j) / (2 * p) == (i + j + k) / (2 * p)) {
-            const int x = v[i + j], y = v[i + j + k];
+            const K x = v[i + j], y = v[i + j + k];
             v[i + j] = x < y ? x : y;
             v[i + j + k] = x < y ? y : x;
           }
@@ -247,8 +317,12 @@ __device__ __forceinline__ void pf_column_median(const unsigned short* col, int 
   hi = v[N / 2];
 }
 
-__global__ void __launch_bounds__(kThreads)
-pf_windows_kernel(const unsigned short* __restrict__ in, int h, int w, const double* __restrict__ sub,
+// T: the pixel type (unsigned short, or double for the float64 frames); MAXR: the tallest window the instantiation takes (48:
+// the EPID configuration, 64: tall leaves, whose columns of more than 32 rows go through a 64-input median network); WPB: waves
+// per workgroup (4 for uint16 pixels; 1 for doubles, whose window block is up to 64 KiB per wave)
+template <typename T, int MAXR, int WPB>
+__global__ void __launch_bounds__(WPB * PL_WAVE)
+pf_windows_kernel(const T* __restrict__ in, int h, int w, const double* __restrict__ sub,
                   const double* __restrict__ div, const int32_t* __restrict__ pk_count,
                   const int32_t* __restrict__ pk_idx, const double* __restrict__ pk_val, int cap,
                   const double* __restrict__ spacing, const int32_t* __restrict__ leaf_top,
@@ -260,13 +334,16 @@ pf_windows_kernel(const unsigned short* __restrict__ in, int h, int w, const dou
   // the CALLER will ask for (the leaf geometry is host knowledge): the fixed 48-row capacity of rounds 1-3 kept three
   // workgroups on a CU where a 26-row bank leaves room for five -- the kernel is one long dependent chain per wave and
   // lives on the number of waves that hide it
+  static_assert(MAXR <= PL_WAVE && WPB >= 1 && WPB <= kThreads / PL_WAVE, "one lane per window row; at most four waves");
+  constexpr bool kF64 = std::is_same<T, double>::value;
+  using K = typename std::conditional<kF64, double, int>::type;    // pixel keys: max, column medians
   extern __shared__ __attribute__((aligned(16))) unsigned char pf_lds[];
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // per wave: [rows_cap row deviations][rows_cap x 128 window pixels]; once the column medians are in registers the same
   // bytes hold the FWXM search (rec_out): [128 profile samples][find_peaks tables]
   unsigned char* const wave_lds = pf_lds + (size_t)wv * wave_bytes;
   double* const s_std_w_ = reinterpret_cast<double*>(wave_lds);
-  unsigned short* const sw_ = reinterpret_cast<unsigned short*>(wave_lds + (size_t)rows_cap * sizeof(double));
+  T* const sw_ = reinterpret_cast<T*>(wave_lds + (size_t)rows_cap * sizeof(double));
   __shared__ Scan pk_scan[kThreads / PL_WAVE];
   __shared__ double pk_red[kThreads / PL_WAVE][2 * (kThreads / PL_WAVE)];
   __shared__ int pk_cnt[kThreads / PL_WAVE];
@@ -274,7 +351,7 @@ pf_windows_kernel(const unsigned short* __restrict__ in, int h, int w, const dou
       o_rb[kThreads / PL_WAVE];
   __shared__ double o_p[kThreads / PL_WAVE][6];
   // window index in 32 bits (the launcher refuses more: the profiles of 2^31 windows would be 2 TB), wave-uniform: scalar
-  const unsigned win = blockIdx.x * (unsigned)(kThreads / PL_WAVE) + (unsigned)wv;
+  const unsigned win = blockIdx.x * (unsigned)WPB + (unsigned)wv;
   if ((int64_t)win >= total_windows) return;
   const int pi = (int)(win % (unsigned)cap);
   const int li = (int)((win / (unsigned)cap) % (unsigned)nleaves);
@@ -310,20 +387,28 @@ pf_windows_kernel(const unsigned short* __restrict__ in, int h, int w, const dou
     leave(3, off);
     return;
   }
-  const unsigned short* f = in + frame * (size_t)h * w;
-  unsigned short* sw = sw_;
+  const T* f = in + frame * (size_t)h * w;
+  T* sw = sw_;
   double* const s_std_w = s_std_w_;
   // the window into LDS, its maximum on the way (element e = lane, lane + 64, ..: row / column advance by carry, no division).
   // EIGHT loads are issued before the first of them is consumed: one load per trip made the wave pay the full memory
   // latency for every 64 pixels (eight dependent round trips for a 12 x 38 window)
-  int vmax = 0;
+  K vmax;
+  if constexpr (kF64) vmax = -__builtin_huge_val();
+  else vmax = 0;
+  // float64 pixels are staged as q itself: one division per pixel instead of one per read (the deviations read each pixel
+  // twice), and since q is non-decreasing in the pixel, the maximum and the column order statistics of the staged values
+  // are those of q -- the same numbers the uint16 form maps through q after selecting
+  [[maybe_unused]] PlQuot kq_stage{};
+  if constexpr (kF64) kq_stage = pl_quot_div(sub[frame], div[frame]);
+  [[maybe_unused]] bool finite = true;             // float64 pixels: no NaN / inf in the window (else the caller refuses the frame)
   {
     int r = lane / ncols, c = lane - r * ncols;
     const int dr = PL_WAVE / ncols, dc = PL_WAVE - dr * ncols;
     const unsigned stride_across = lr ? 1u : (unsigned)w, stride_along = lr ? (unsigned)w : 1u;   // scalars: no branch per load
     const int total = nrows * ncols;
     for (int e0 = lane; e0 < total + lane; e0 += 8 * PL_WAVE) {      // wave-uniform trip count
-      unsigned short v[8];
+      T v[8];
       int rr = r, cc = c;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
@@ -342,8 +427,15 @@ pf_windows_kernel(const unsigned short* __restrict__ in, int h, int w, const dou
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         if (e0 + k * PL_WAVE < total) {
-          sw[e0 + k * PL_WAVE] = v[k];
-          vmax = max(vmax, (int)v[k]);
+          if constexpr (kF64) {
+            const double qv = pl_quot(kq_stage, v[k]);
+            sw[e0 + k * PL_WAVE] = qv;
+            vmax = qv > vmax ? qv : vmax;
+            finite = finite && v[k] - v[k] == 0.0;
+          } else {
+            sw[e0 + k * PL_WAVE] = v[k];
+            vmax = max(vmax, (int)v[k]);
+          }
         }
       }
       r = rr;
@@ -352,12 +444,24 @@ pf_windows_kernel(const unsigned short* __restrict__ in, int h, int w, const dou
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
-  const PlQuot kq = pl_quot_make(sub[frame], div[frame]);
-  auto q = [&](int r, int c) { return pl_quot(kq, (double)sw[r * ncols + c]); };
+  if constexpr (kF64) {
+    if (__ballot(!finite)) {                         // wave-uniform: nothing non-finite reaches the median or the FWXM search
+      leave(3, off);
+      return;
+    }
+  }
+  const PlQuot kq = pf_quot<T>(sub[frame], div[frame]);
+  auto q = [&](int r, int c) {
+    if constexpr (kF64) return (double)sw[r * ncols + c];
+    else return pl_quot(kq, (double)sw[r * ncols + c]);
+  };
 
-  // np.max(window) > height_threshold * picket_peak_val   (q is monotone in the integer pixel)
-  vmax = pl_wave_reduce_idem(vmax, [](int a, int b) { return a > b ? a : b; });
-  const bool above = pl_quot(kq, (double)vmax) > height_threshold * pk_val[frame * cap + pi];
+  // np.max(window) > height_threshold * picket_peak_val   (q is monotone in the pixel)
+  vmax = pl_wave_reduce_idem(vmax, [](K a, K b) { return a > b ? a : b; });
+  double qmax;
+  if constexpr (kF64) qmax = vmax;
+  else qmax = pl_quot(kq, (double)vmax);
+  const bool above = qmax > height_threshold * pk_val[frame * cap + pi];
 
   // np.std(window, axis=1) with numpy's pairwise summation order (one block of ncols <= 128 values: eight running sums
   // r[j] over elements j, j+8, ..., combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the n % 8 tail).  EIGHT lanes
@@ -373,6 +477,7 @@ pf_windows_kernel(const unsigned short* __restrict__ in, int h, int w, const dou
   // only a window inside the margin (or with `exact_std`) evaluates numpy's sequence below.  r05a stopwatch: the float64
   // stage was 180 of the kernel's 485 us.
   bool decided = false, not_edge = false;
+  if constexpr (!kF64) {                                     // (integer moments need integer pixels)
   if (!exact_std) {
     const int j = lane & 7, gr = lane >> 3;
     for (int row0 = 0; row0 < nrows; row0 += 8) {           // wave-uniform trip count
@@ -414,6 +519,7 @@ pf_windows_kernel(const unsigned short* __restrict__ in, int h, int w, const dou
     if (max_hi < edge_threshold * med_lo) { decided = true; not_edge = true; }
     else if (max_lo >= edge_threshold * med_hi) { decided = true; not_edge = false; }
     __builtin_amdgcn_wave_barrier();                         // (the exact stage below rewrites s_std_w)
+  }
   }
   if (!decided) {
 #if PL_PF_VARIANT == 1                                     // stopwatch: no deviation stage (wrong edge test)
@@ -462,7 +568,7 @@ pf_windows_kernel(const unsigned short* __restrict__ in, int h, int w, const dou
 #endif
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
-  // max(std) < edge_threshold * np.median(std): lane a ranks std[a] (nrows <= 48 <= 64 lanes)
+  // max(std) < edge_threshold * np.median(std): lane a ranks std[a] (nrows <= MAXR <= 64 lanes)
   double smax, med;
   {
     const bool act = lane < nrows;
@@ -492,7 +598,7 @@ pf_windows_kernel(const unsigned short* __restrict__ in, int h, int w, const dou
     const int c = lane + slot * PL_WAVE;
     if (c >= ncols) continue;
     const int k_hi = nrows / 2, k_lo = (nrows & 1) ? k_hi : k_hi - 1;
-    int v_lo = 0, v_hi = 0;
+    K v_lo = 0, v_hi = 0;
 #if PL_PF_VARIANT == 2                                     // stopwatch: no column median (row 0 instead)
     v_lo = v_hi = sw[c];
 #else
@@ -503,6 +609,9 @@ pf_windows_kernel(const unsigned short* __restrict__ in, int h, int w, const dou
       // ranked by counting (n^2 LDS reads beyond 16 rows: 20 us for a 26-row leaf).
       if (nrows <= 16) pf_column_median<16>(sw + c, ncols, nrows, v_lo, v_hi);
       else pf_column_median<32>(sw + c, ncols, nrows, v_lo, v_hi);
+      if (nrows & 1) v_hi = v_lo;
+    } else if constexpr (MAXR > kMaxRows) {          // 33 .. 64 rows (tall leaves): the 64-input network
+      pf_column_median<64>(sw + c, ncols, nrows, v_lo, v_hi);
       if (nrows & 1) v_hi = v_lo;
     } else {
       for (int a = 0; a < nrows; ++a) {
@@ -517,8 +626,12 @@ pf_windows_kernel(const unsigned short* __restrict__ in, int h, int w, const dou
       }
     }
 #endif
-    const double qh = pl_quot(kq, (double)v_hi);
-    pvr[slot] = (nrows & 1) ? qh : (pl_quot(kq, (double)v_lo) + qh) / 2.0;
+    if constexpr (kF64) {
+      pvr[slot] = (nrows & 1) ? v_hi : (v_lo + v_hi) / 2.0;
+    } else {
+      const double qh = pl_quot(kq, (double)v_hi);
+      pvr[slot] = (nrows & 1) ? qh : (pl_quot(kq, (double)v_lo) + qh) / 2.0;
+    }
   }
   // ground (values - min) then normalize (/ max of the grounded profile)
   const bool has0 = lane < ncols, has1 = lane + PL_WAVE < ncols;
@@ -600,6 +713,24 @@ extern "C" int pl_scaled_colmean(const uint16_t* in, int64_t n, int h, int w, co
   return pl_check_launch("pl_scaled_colmean");
 }
 
+/* np.mean(q, 0) of float64 frames: see pylinac_hip.h */
+extern "C" int pl_scaled_colmean_f64(const double* in, int64_t n, int h, int w, const double* d_sub, const double* d_div,
+                                     double* d_out, void* stream) {
+  PL_REQUIRE(in && d_sub && d_div && d_out, "null pointer");
+  PL_REQUIRE(n >= 0 && h > 0 && w > 0, "bad shape");
+  if (n == 0) return PL_OK;
+  const bool pairs = (w & 1) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+  const int64_t groups = n * (int64_t)(pairs ? w / 2 : w);
+  PL_REQUIRE(pl_cdiv(groups, kThreads) <= 0x7fffffffLL, "batch too large");
+  if (pairs)
+    hipLaunchKernelGGL((scaled_colmean_f64_kernel<2, 16>), dim3((unsigned)pl_cdiv(groups, kThreads)), dim3(kThreads), 0,
+                       (hipStream_t)stream, in, h, w, groups, d_sub, d_div, d_out);
+  else
+    hipLaunchKernelGGL((scaled_colmean_f64_kernel<1, 16>), dim3((unsigned)pl_cdiv(groups, kThreads)), dim3(kThreads), 0,
+                       (hipStream_t)stream, in, h, w, groups, d_sub, d_div, d_out);
+  return pl_check_launch("pl_scaled_colmean_f64");
+}
+
 extern "C" int pl_pf_pickets(const int32_t* d_count, const double* d_props, int cap, const double* d_prof, int w,
                              int64_t n, int32_t* d_pk_idx, double* d_pk_val, double* d_spacing, void* stream) {
   PL_REQUIRE(d_count && d_props && d_prof && d_pk_idx && d_pk_val && d_spacing, "null pointer");
@@ -616,6 +747,7 @@ extern "C" int pl_pf_windows_rows(const uint16_t* in, int64_t n, int h, int w, c
                                   int nleaves, int max_rows, double height_threshold, double edge_threshold, int lmax,
                                   double* d_prof, int32_t* d_len, double* d_offset, int32_t* d_status, void* stream);
 
+// the entry point without a row bound keeps the 48-row window block of the EPID configuration
 extern "C" int pl_pf_windows(const uint16_t* in, int64_t n, int h, int w, const double* d_sub, const double* d_div,
                              const int32_t* d_pk_count, const int32_t* d_pk_idx, const double* d_pk_val, int cap,
                              const double* d_spacing, const int32_t* d_leaf_top, const int32_t* d_leaf_bottom,
@@ -626,8 +758,8 @@ extern "C" int pl_pf_windows(const uint16_t* in, int64_t n, int h, int w, const 
 }
 
 // per-wave LDS of pf_windows_kernel: the window block, or (fused FWXM search) the profile + find_peaks tables, whichever is larger
-static size_t pf_wave_bytes(int rows_cap, bool fused) {
-  size_t wb = (size_t)rows_cap * (sizeof(double) + (size_t)kMaxCols * sizeof(unsigned short));
+static size_t pf_wave_bytes(int rows_cap, bool fused, size_t pixel_bytes = sizeof(unsigned short)) {
+  size_t wb = (size_t)rows_cap * (sizeof(double) + (size_t)kMaxCols * pixel_bytes);
   if (fused) {
     constexpr int maxc = kMaxCols / 2 + 1;
     size_t sb = (size_t)kMaxCols * sizeof(double) + (((size_t)maxc * (8 + 8 + 4 * 4) + 8 + (size_t)kMaxCols * 8 + 15) & ~(size_t)15);
@@ -636,28 +768,78 @@ static size_t pf_wave_bytes(int rows_cap, bool fused) {
   return (wb + 15) & ~(size_t)15;
 }
 
-// max_rows: the tallest leaf window (bottom - top) of the call, 1 .. 48 -- windows taller than that get status 3
+// One launch of pf_windows_kernel<T, MAXR, WPB> for rows_cap <= MAXR.  Dynamic LDS beyond 64 KiB (the tall-leaf and float64
+// instantiations only: 48-row uint16 blocks are 4 x 12.7 KiB) is opted into once per instantiation.
+template <typename T, int MAXR, int WPB>
+static int pf_windows_launch(const T* in, int h, int w, const double* d_sub, const double* d_div, const int32_t* d_pk_count,
+                             const int32_t* d_pk_idx, const double* d_pk_val, int cap, const double* d_spacing,
+                             const int32_t* d_lo, const int32_t* d_hi, int nleaves, double height_threshold,
+                             double edge_threshold, int lmax, double* d_prof, int32_t* d_len, double* d_offset,
+                             int32_t* d_status, int64_t total, int rows_cap, int lr, bool fused, const pl_peak_params& fw,
+                             double* d_rec, int exact, void* stream, const char* who) {
+  const size_t wb = pf_wave_bytes(rows_cap, fused, sizeof(T));
+  const size_t lds = wb * WPB;
+  if (lds > 64 * 1024) {
+    static std::atomic<size_t> attr{0};
+    if (lds > attr) {
+      hipError_t e = hipFuncSetAttribute((const void*)pf_windows_kernel<T, MAXR, WPB>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)lds);
+      if (e != hipSuccess) { pl_set_error("%s: LDS attribute: %s", who, hipGetErrorString(e)); return PL_ERR_HIP; }
+      attr = lds;
+    }
+  }
+  hipLaunchKernelGGL((pf_windows_kernel<T, MAXR, WPB>), dim3((unsigned)pl_cdiv(total, WPB)), dim3(WPB * PL_WAVE), lds,
+                     (hipStream_t)stream, in, h, w, d_sub, d_div, d_pk_count, d_pk_idx, d_pk_val, cap, d_spacing, d_lo, d_hi,
+                     nleaves, height_threshold, edge_threshold, lmax, d_prof, d_len, d_offset, d_status, total, rows_cap, lr,
+                     (int)wb, fw, d_rec, exact);
+  return pl_check_launch(who);
+}
+
+// uint16 windows: the 48-row instantiation (today's launch: four waves, 4 x rows_cap x 264 bytes) up to 48 rows, the 64-row one
+// (64-input column-median network, up to 4 x 16.5 KiB) for taller leaves
+static int pf_windows_u16(const uint16_t* in, int h, int w, const double* d_sub, const double* d_div, const int32_t* d_pk_count,
+                          const int32_t* d_pk_idx, const double* d_pk_val, int cap, const double* d_spacing, const int32_t* d_lo,
+                          const int32_t* d_hi, int nleaves, double height_threshold, double edge_threshold, int lmax,
+                          double* d_prof, int32_t* d_len, double* d_offset, int32_t* d_status, int64_t total, int max_rows,
+                          int lr, bool fused, const pl_peak_params& fw, double* d_rec, int exact, void* stream, const char* who) {
+  const int rows_cap = (max_rows + 1) & ~1;          // even: the window planes stay 4-byte aligned behind the row deviations
+  if (rows_cap <= kMaxRows)
+    return pf_windows_launch<unsigned short, kMaxRows, kThreads / PL_WAVE>(
+        in, h, w, d_sub, d_div, d_pk_count, d_pk_idx, d_pk_val, cap, d_spacing, d_lo, d_hi, nleaves, height_threshold,
+        edge_threshold, lmax, d_prof, d_len, d_offset, d_status, total, rows_cap, lr, fused, fw, d_rec, exact, stream, who);
+  return pf_windows_launch<unsigned short, kMaxRowsTall, kThreads / PL_WAVE>(
+      in, h, w, d_sub, d_div, d_pk_count, d_pk_idx, d_pk_val, cap, d_spacing, d_lo, d_hi, nleaves, height_threshold,
+      edge_threshold, lmax, d_prof, d_len, d_offset, d_status, total, rows_cap, lr, fused, fw, d_rec, exact, stream, who);
+}
+
+// max_rows: the tallest leaf window (bottom - top) of the call, 1 .. 64 -- windows taller than that get status 3
 extern "C" int pl_pf_windows_rows(const uint16_t* in, int64_t n, int h, int w, const double* d_sub, const double* d_div,
                                   const int32_t* d_pk_count, const int32_t* d_pk_idx, const double* d_pk_val, int cap,
                                   const double* d_spacing, const int32_t* d_leaf_top, const int32_t* d_leaf_bottom,
                                   int nleaves, int max_rows, double height_threshold, double edge_threshold, int lmax,
                                   double* d_prof, int32_t* d_len, double* d_offset, int32_t* d_status, void* stream) {
-  PL_REQUIRE(max_rows >= 1 && max_rows <= kMaxRows, "max_rows 1..48");
+  PL_REQUIRE(max_rows >= 1 && max_rows <= kMaxRowsTall, "max_rows 1..64");
   PL_REQUIRE(in && d_sub && d_div && d_pk_count && d_pk_idx && d_pk_val && d_spacing && d_leaf_top && d_leaf_bottom &&
                  d_prof && d_len && d_offset && d_status, "null pointer");
   PL_REQUIRE(n >= 0 && h > 0 && w > 0 && cap > 0 && nleaves > 0 && lmax >= kMaxCols, "bad shape (lmax >= 128)");
   if (n == 0) return PL_OK;
   const int64_t total = n * (int64_t)nleaves * cap;
-  const int64_t blocks = pl_cdiv(total, kThreads / PL_WAVE);
   PL_REQUIRE(total <= 0x7fffffffLL, "batch too large");
-  const int rows_cap = (max_rows + 1) & ~1;          // even: the window planes stay 4-byte aligned behind the row deviations
-  const size_t wb = pf_wave_bytes(rows_cap, false);
-  hipLaunchKernelGGL(pf_windows_kernel, dim3((unsigned)blocks), dim3(kThreads), wb * (kThreads / PL_WAVE), (hipStream_t)stream, in, h, w,
-                     d_sub, d_div, d_pk_count, d_pk_idx, d_pk_val, cap, d_spacing, d_leaf_top, d_leaf_bottom, nleaves,
-                     height_threshold, edge_threshold, lmax, d_prof, d_len, d_offset, d_status, total, rows_cap, 0, (int)wb,
-                     pl_peak_params{}, nullptr, 0);
-  return pl_check_launch("pl_pf_windows");
+  return pf_windows_u16(in, h, w, d_sub, d_div, d_pk_count, d_pk_idx, d_pk_val, cap, d_spacing, d_leaf_top, d_leaf_bottom, nleaves,
+                        height_threshold, edge_threshold, lmax, d_prof, d_len, d_offset, d_status, total, max_rows, 0, false,
+                        pl_peak_params{}, nullptr, 0, stream, "pl_pf_windows");
 }
+
+#define PF_MEASURE_CHECKS                                                                                                        \
+  PL_REQUIRE(max_rows >= 1 && max_rows <= kMaxRowsTall, "max_rows 1..64");                                                       \
+  PL_REQUIRE(orientation == 0 || orientation == 1, "orientation 0 (UP_DOWN) or 1 (LEFT_RIGHT)");                                 \
+  PL_REQUIRE(in && d_sub && d_div && d_pk_count && d_pk_idx && d_pk_val && d_spacing && d_leaf_lo && d_leaf_hi && fwxm_params && \
+                 d_rec && d_status, "null pointer");                                                                             \
+  PL_REQUIRE(n >= 0 && h > 0 && w > 0 && cap > 0 && nleaves > 0 && (!d_prof || lmax >= kMaxCols), "bad shape (lmax >= 128)");   \
+  PL_REQUIRE(fwxm_params->distance >= 1, "distance must be >= 1");                                                               \
+  if (n == 0) return PL_OK;                                                                                                      \
+  const int64_t total = n * (int64_t)nleaves * cap;                                                                              \
+  PL_REQUIRE(total <= 0x7fffffffLL, "batch too large")
 
 /* windows + FWXM positions in one launch, either orientation: see pylinac_hip.h */
 extern "C" int pl_pf_measure(const uint16_t* in, int64_t n, int h, int w, int orientation, const double* d_sub, const double* d_div,
@@ -666,24 +848,28 @@ extern "C" int pl_pf_measure(const uint16_t* in, int64_t n, int h, int w, int or
                              int max_rows, double height_threshold, double edge_threshold, int exact_deviation,
                              const pl_peak_params* fwxm_params, double* d_rec, int32_t* d_status, double* d_prof, int lmax,
                              void* stream) {
-  PL_REQUIRE(max_rows >= 1 && max_rows <= kMaxRows, "max_rows 1..48");
-  PL_REQUIRE(orientation == 0 || orientation == 1, "orientation 0 (UP_DOWN) or 1 (LEFT_RIGHT)");
-  PL_REQUIRE(in && d_sub && d_div && d_pk_count && d_pk_idx && d_pk_val && d_spacing && d_leaf_lo && d_leaf_hi && fwxm_params &&
-                 d_rec && d_status, "null pointer");
-  PL_REQUIRE(n >= 0 && h > 0 && w > 0 && cap > 0 && nleaves > 0 && (!d_prof || lmax >= kMaxCols), "bad shape (lmax >= 128)");
-  PL_REQUIRE(fwxm_params->distance >= 1, "distance must be >= 1");
-  if (n == 0) return PL_OK;
-  const int64_t total = n * (int64_t)nleaves * cap;
-  const int64_t blocks = pl_cdiv(total, kThreads / PL_WAVE);
-  PL_REQUIRE(total <= 0x7fffffffLL, "batch too large");
-  const int rows_cap = (max_rows + 1) & ~1;
-  const size_t wb = pf_wave_bytes(rows_cap, true);
-  hipLaunchKernelGGL(pf_windows_kernel, dim3((unsigned)blocks), dim3(kThreads), wb * (kThreads / PL_WAVE), (hipStream_t)stream, in, h, w,
-                     d_sub, d_div, d_pk_count, d_pk_idx, d_pk_val, cap, d_spacing, d_leaf_lo, d_leaf_hi, nleaves,
-                     height_threshold, edge_threshold, lmax, d_prof, (int32_t*)nullptr, (double*)nullptr, d_status, total, rows_cap,
-                     orientation, (int)wb, *fwxm_params, d_rec, exact_deviation ? 1 : 0);
-  return pl_check_launch("pl_pf_measure");
+  PF_MEASURE_CHECKS;
+  return pf_windows_u16(in, h, w, d_sub, d_div, d_pk_count, d_pk_idx, d_pk_val, cap, d_spacing, d_leaf_lo, d_leaf_hi, nleaves,
+                        height_threshold, edge_threshold, lmax, d_prof, (int32_t*)nullptr, (double*)nullptr, d_status, total,
+                        max_rows, orientation, true, *fwxm_params, d_rec, exact_deviation ? 1 : 0, stream, "pl_pf_measure");
 }
+
+/* pl_pf_measure on float64 frames: see pylinac_hip.h.  One wave per workgroup: a window block of float64 pixels is
+ * rows_cap x 1032 bytes (26.8 KiB for the 26-row leaves of an aS1000 at 0.39 mm: five waves per CU; 66 KiB at 64 rows: two),
+ * and one-wave workgroups let the CU's 160 KiB hold as many of them as fit. */
+extern "C" int pl_pf_measure_f64(const double* in, int64_t n, int h, int w, int orientation, const double* d_sub,
+                                 const double* d_div, const int32_t* d_pk_count, const int32_t* d_pk_idx, const double* d_pk_val,
+                                 int cap, const double* d_spacing, const int32_t* d_leaf_lo, const int32_t* d_leaf_hi, int nleaves,
+                                 int max_rows, double height_threshold, double edge_threshold, const pl_peak_params* fwxm_params,
+                                 double* d_rec, int32_t* d_status, double* d_prof, int lmax, void* stream) {
+  PF_MEASURE_CHECKS;
+  const int rows_cap = (max_rows + 1) & ~1;
+  return pf_windows_launch<double, kMaxRowsTall, 1>(in, h, w, d_sub, d_div, d_pk_count, d_pk_idx, d_pk_val, cap, d_spacing,
+                                                     d_leaf_lo, d_leaf_hi, nleaves, height_threshold, edge_threshold, lmax, d_prof,
+                                                     (int32_t*)nullptr, (double*)nullptr, d_status, total, rows_cap, orientation,
+                                                     true, *fwxm_params, d_rec, 1, stream, "pl_pf_measure_f64");
+}
+#undef PF_MEASURE_CHECKS
 
 extern "C" int pl_pf_positions(const int32_t* d_status, const double* d_fwxm, const double* d_offset, int64_t m,
                                double* d_pos, void* stream) {
@@ -695,6 +881,27 @@ extern "C" int pl_pf_positions(const int32_t* d_status, const double* d_fwxm, co
   return pl_check_launch("pl_pf_positions");
 }
 
+// rows of at most 32 KiB of pixels staged per wave (16384 uint16, 4096 float64)
+template <typename T>
+static int scaled_rowmean_launch(const T* in, int64_t n, int h, int w, const double* d_sub, const double* d_div,
+                                 const int32_t* d_leaf_start, const int32_t* d_leaf_len, int nleaves, const int32_t* d_program,
+                                 int nprog, double* d_out, void* stream, const char* who) {
+  if (n == 0) return PL_OK;
+  const int64_t rows = n * (int64_t)h;
+  if (pl_cdiv(rows, kThreads / PL_WAVE) > 0x7fffffffLL) { pl_set_error("%s: batch too large", who); return PL_ERR_INVALID_ARG; }
+  const size_t wave_bytes = (((size_t)w * sizeof(T) + 15) & ~(size_t)15) + (size_t)(kRmMaxLeaves + 16) * sizeof(double);
+  const size_t lds = wave_bytes * (kThreads / PL_WAVE);
+  static std::atomic<size_t> attr{0};
+  if (lds > 64 * 1024 && lds > attr) {
+    hipError_t e = hipFuncSetAttribute((const void*)scaled_rowmean_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) { pl_set_error("%s: LDS attribute: %s", who, hipGetErrorString(e)); return PL_ERR_HIP; }
+    attr = lds;
+  }
+  hipLaunchKernelGGL(scaled_rowmean_kernel<T>, dim3((unsigned)pl_cdiv(rows, kThreads / PL_WAVE)), dim3(kThreads), lds,
+                     (hipStream_t)stream, in, h, w, rows, d_sub, d_div, d_leaf_start, d_leaf_len, nleaves, d_program, nprog, d_out);
+  return pl_check_launch(who);
+}
+
 /* np.mean(q, 1) -> d_out float64 [n][h] in numpy's pairwise order; the summation tree (leaves, postfix program) of a row of
  * w values is laid out by the caller: see scaled_rowmean_kernel */
 extern "C" int pl_scaled_rowmean(const uint16_t* in, int64_t n, int h, int w, const double* d_sub, const double* d_div,
@@ -703,18 +910,16 @@ extern "C" int pl_scaled_rowmean(const uint16_t* in, int64_t n, int h, int w, co
   PL_REQUIRE(in && d_sub && d_div && d_leaf_start && d_leaf_len && d_program && d_out, "null pointer");
   PL_REQUIRE(n >= 0 && h > 0 && w > 0 && w <= 16384, "bad shape (rows of at most 16384 pixels)");
   PL_REQUIRE(nleaves >= 1 && nleaves <= kRmMaxLeaves && nprog == 2 * nleaves - 1, "a summation tree of 1..256 leaves");
-  if (n == 0) return PL_OK;
-  const int64_t rows = n * (int64_t)h;
-  PL_REQUIRE(pl_cdiv(rows, kThreads / PL_WAVE) <= 0x7fffffffLL, "batch too large");
-  const size_t wave_bytes = (((size_t)w * 2 + 15) & ~(size_t)15) + (size_t)(kRmMaxLeaves + 16) * sizeof(double);
-  const size_t lds = wave_bytes * (kThreads / PL_WAVE);
-  static std::atomic<size_t> attr{0};
-  if (lds > 64 * 1024 && lds > attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)scaled_rowmean_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { pl_set_error("pl_scaled_rowmean: LDS attribute: %s", hipGetErrorString(e)); return PL_ERR_HIP; }
-    attr = lds;
-  }
-  hipLaunchKernelGGL(scaled_rowmean_kernel, dim3((unsigned)pl_cdiv(rows, kThreads / PL_WAVE)), dim3(kThreads), lds, (hipStream_t)stream,
-                     in, h, w, rows, d_sub, d_div, d_leaf_start, d_leaf_len, nleaves, d_program, nprog, d_out);
-  return pl_check_launch("pl_scaled_rowmean");
+  return scaled_rowmean_launch(in, n, h, w, d_sub, d_div, d_leaf_start, d_leaf_len, nleaves, d_program, nprog, d_out, stream,
+                               "pl_scaled_rowmean");
+}
+
+extern "C" int pl_scaled_rowmean_f64(const double* in, int64_t n, int h, int w, const double* d_sub, const double* d_div,
+                                     const int32_t* d_leaf_start, const int32_t* d_leaf_len, int nleaves, const int32_t* d_program,
+                                     int nprog, double* d_out, void* stream) {
+  PL_REQUIRE(in && d_sub && d_div && d_leaf_start && d_leaf_len && d_program && d_out, "null pointer");
+  PL_REQUIRE(n >= 0 && h > 0 && w > 0 && w <= 4096, "bad shape (rows of at most 4096 pixels)");
+  PL_REQUIRE(nleaves >= 1 && nleaves <= kRmMaxLeaves && nprog == 2 * nleaves - 1, "a summation tree of 1..256 leaves");
+  return scaled_rowmean_launch(in, n, h, w, d_sub, d_div, d_leaf_start, d_leaf_len, nleaves, d_program, nprog, d_out, stream,
+                               "pl_scaled_rowmean_f64");
 }

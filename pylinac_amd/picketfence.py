@@ -5,7 +5,9 @@ Mirrors the per-image part of ``PicketFence.analyze`` for UP_DOWN pickets
 leaf pair in view and every picket the MLC window, the ``_is_mlc_peak_in_window`` test and the FWXM
 centre of the window's median profile.  The input batch is uint16 ``[N,H,W]`` frames AFTER the
 constructor's crop (picketfence.py:214-215); ground()/normalize() (:322-323) are folded into the
-kernels as the float64 quotient ``(a - min) / (max - min)``.
+kernels as the float64 quotient ``(a - min) / (max - min)``.  int16 frames and float64 frames holding
+integers go through an exact uint16 bridge; float64 frames with fractional values (a rescaled DICOM
+series) are measured on their own float64 kernels with ``measure_fractional=True``.
 
 The per-dataset post-processing of the reference (dropping leaf rows without the modal number of
 kisses :810-824, per-picket line fits :831-843, error in mm :1701-1718) works on the returned
@@ -96,7 +98,8 @@ def analyze_batch(frames: torch.Tensor, dpmm: float, mlc: str = "MILLENNIUM", nu
                   leaf_analysis_width_ratio: float = 0.4, height_threshold: float = 0.5,
                   edge_threshold: float = 1.5, peak_sort: str = "peak_heights",
                   required_prominence: float = 0.2, fwxm: int = 50, cap: int | None = None,
-                  orientation: str = "UP_DOWN", separate_leaves: bool = False, exact_deviation: bool = False) -> PFBatchResult:
+                  orientation: str = "UP_DOWN", separate_leaves: bool = False, exact_deviation: bool = False,
+                  measure_fractional: bool = False) -> PFBatchResult:
     """The per-image measurement of ``PicketFence.analyze`` (picketfence.py:745-803, 1605-1628) for a resident batch, in five
     launches: min / max (ground + normalize folded into every later read), leaf profile, picket peaks, picket table, and ONE
     kernel for all leaf x picket windows (window test, median profile, FWXM search, position).  ``orientation``: "UP_DOWN"
@@ -104,17 +107,26 @@ def analyze_batch(frames: torch.Tensor, dpmm: float, mlc: str = "MILLENNIUM", nu
     transposed).  ``separate_leaves``: also return both leaf-end positions per window.  ``cap`` = picket slots per frame
     (default ``num_pickets`` when given, else 16).  ``exact_deviation=True`` makes every window evaluate numpy's float64
     ``np.std`` sequence for the edge test instead of deciding it from exact integer row moments where the margin allows
-    (identical results; a test knob)."""
+    (identical results; a test knob).
+
+    Input: uint16, int16 (range up to 32767) or float64 frames.  By default a float64 frame must hold integers (status 3 in
+    every window of a frame that does not).  ``measure_fractional=True`` measures float64 batches whole on float64 kernels
+    instead -- fractional values (``dicom.load_frames`` with a non-integer RescaleSlope) included, integer-valued frames with
+    the same bits as the default; a frame holding a NaN or an infinity gets status 3 in every window.  Windows taller than 64
+    rows (the leaf width in pixels) or wider than 128 columns (the picket spacing) get status 3; LEFT_RIGHT float64 frames
+    may be at most 4096 columns wide."""
     x = ops._frames(frames)
     unfit = None
-    if x.dtype in (torch.int16, torch.float64):
+    f64 = bool(measure_fractional) and x.dtype == torch.float64     # q = (a - min) / (max - min) by true division
+    if x.dtype in (torch.int16, torch.float64) and not f64:
         # what the reference's loader may hand over instead of uint16: a signed panel's int16, or float64 holding integers
         # (``dtype=float``; rescale tags with an integer slope and intercept).  ground() / normalize() (picketfence.py:322-323)
         # only see a - min, which pl_to_u16_exact forms exactly; frames it cannot represent -- non-integer float64 values,
         # an int16 range beyond 32767 where the reference's own ground() wraps -- come back with status 3 in every window
         x, unfit = ops.to_u16_exact(x)
-    elif x.dtype != torch.uint16:
-        raise TypeError("analyze_batch takes uint16 frames, int16 frames, or float64 frames holding integers")
+    elif x.dtype != torch.uint16 and not f64:
+        raise TypeError("analyze_batch takes uint16 frames, int16 frames, or float64 frames (holding integers unless "
+                        "measure_fractional=True)")
     if orientation not in ("UP_DOWN", "LEFT_RIGHT"):
         raise ValueError("orientation must be 'UP_DOWN' or 'LEFT_RIGHT'")
     lr = orientation == "LEFT_RIGHT"
@@ -133,11 +145,16 @@ def analyze_batch(frames: torch.Tensor, dpmm: float, mlc: str = "MILLENNIUM", nu
         if key not in _PLAN_CACHE:
             _PLAN_CACHE[key] = tuple(torch.from_numpy(a).to(dev) for a in pairwise_plan(w))
         ls, ll, pg = _PLAN_CACHE[key]
-        check(lib.pl_scaled_rowmean(x.data_ptr(), n, h, w, vmin.data_ptr(), gmax.data_ptr(), ls.data_ptr(), ll.data_ptr(),
-                                    ls.numel(), pg.data_ptr(), pg.numel(), leaf_prof.data_ptr(), st), "pl_scaled_rowmean")
+        rowmean = lib.pl_scaled_rowmean_f64 if f64 else lib.pl_scaled_rowmean
+        check(rowmean(x.data_ptr(), n, h, w, vmin.data_ptr(), gmax.data_ptr(), ls.data_ptr(), ll.data_ptr(),
+                      ls.numel(), pg.data_ptr(), pg.numel(), leaf_prof.data_ptr(), st), "pl_scaled_rowmean")
     else:
-        check(lib.pl_scaled_colmean(x.data_ptr(), n, h, w, vmin.data_ptr(), gmax.data_ptr(), leaf_prof.data_ptr(), st),
-              "pl_scaled_colmean")
+        colmean = lib.pl_scaled_colmean_f64 if f64 else lib.pl_scaled_colmean
+        check(colmean(x.data_ptr(), n, h, w, vmin.data_ptr(), gmax.data_ptr(), leaf_prof.data_ptr(), st), "pl_scaled_colmean")
+    if f64:
+        # a NaN or an infinity in a frame: an infinite minimum or maximum makes max - min non-finite, and every pixel is in one
+        # leaf-profile sum, so a NaN pixel leaves a NaN there (a constant frame's 0 / 0 profile is the uint16 path's too)
+        unfit = ~torch.isfinite(gmax) | (torch.isnan(leaf_prof).any(1) & (gmax > 0))
     leaf_prof = ops.normalize(leaf_prof.unsqueeze(1)).squeeze(1).contiguous()      # MultiProfile.normalize()
     peaks = ops.find_peaks_batch(leaf_prof, cap=cap, threshold=height_threshold, peak_separation=0.02,
                                  max_number=num_pickets, peak_sort=peak_sort,
@@ -165,18 +182,25 @@ def analyze_batch(frames: torch.Tensor, dpmm: float, mlc: str = "MILLENNIUM", nu
         _PLAN_CACHE[key] = (torch.tensor(los, dtype=torch.int32, device=dev), torch.tensor(his, dtype=torch.int32, device=dev))
     d_lo, d_hi = _PLAN_CACHE[key]
     m = n * nl * cap
-    # the widest leaf in pixels: the kernel's LDS per wave follows it.  48 is the limit (status 3 beyond): 10 mm leaves (the
-    # widest of every supported bank) on the finest supported panel at isocentre scale (aS1200, 0.336 mm at SID 1500) are 45
-    max_rows = min(max([b - t for t, b in zip(los, his)] + [1]), 48)
+    # the widest leaf in pixels: the kernel's LDS per wave follows it.  64 is the limit (status 3 beyond): 10 mm leaves (the
+    # widest of every supported bank) on the finest supported panel at isocentre scale (aS1200, 0.336 mm at SID 1500) are 45,
+    # on a 150 dpi film scan 59; up to 48 rows the kernel runs in its EPID configuration
+    max_rows = min(max([b - t for t, b in zip(los, his)] + [1]), 64)
     fw = ops.make_peak_params(128, fwxm_height=fwxm / 100, max_number=1)                 # FWXMProfile.field_edge_idx
     rec = torch.empty((m, 3), dtype=torch.float64, device=dev)
     status = torch.empty(m, dtype=torch.int32, device=dev)
     import ctypes as C
-    check(lib.pl_pf_measure(x.data_ptr(), n, h, w, 1 if lr else 0, vmin.data_ptr(), gmax.data_ptr(), peaks.count.data_ptr(),
-                            pk_idx.data_ptr(), pk_val.data_ptr(), cap, spacing.data_ptr(), d_lo.data_ptr(), d_hi.data_ptr(), nl,
-                            max_rows, float(height_threshold), float(edge_threshold), 1 if exact_deviation else 0, C.byref(fw),
-                            rec.data_ptr(),
-                            status.data_ptr(), 0, 0, st), "pl_pf_measure")
+    if f64:
+        check(lib.pl_pf_measure_f64(x.data_ptr(), n, h, w, 1 if lr else 0, vmin.data_ptr(), gmax.data_ptr(),
+                                    peaks.count.data_ptr(), pk_idx.data_ptr(), pk_val.data_ptr(), cap, spacing.data_ptr(),
+                                    d_lo.data_ptr(), d_hi.data_ptr(), nl, max_rows, float(height_threshold),
+                                    float(edge_threshold), C.byref(fw), rec.data_ptr(), status.data_ptr(), 0, 0, st),
+              "pl_pf_measure_f64")
+    else:
+        check(lib.pl_pf_measure(x.data_ptr(), n, h, w, 1 if lr else 0, vmin.data_ptr(), gmax.data_ptr(), peaks.count.data_ptr(),
+                                pk_idx.data_ptr(), pk_val.data_ptr(), cap, spacing.data_ptr(), d_lo.data_ptr(), d_hi.data_ptr(),
+                                nl, max_rows, float(height_threshold), float(edge_threshold), 1 if exact_deviation else 0,
+                                C.byref(fw), rec.data_ptr(), status.data_ptr(), 0, 0, st), "pl_pf_measure")
     rec = rec.view(n, nl, cap, 3)
     if unfit is not None:                                   # (device-side selects: no synchronisation)
         bad = (unfit != 0).view(n, 1, 1)
