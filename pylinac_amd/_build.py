@@ -6,7 +6,6 @@ the GPU box by gpurun).
 """
 from __future__ import annotations
 
-import hashlib
 import os
 import shutil
 import subprocess
@@ -60,22 +59,15 @@ def _stale(target: Path, deps: list[Path]) -> bool:
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     cc = hipcc()
-    extra = os.environ.get("PL_EXTRA_HIPCC_FLAGS", "").split()
-    # a variant build (e.g. -DPL_OTSU_VARIANT=1 compiles a stopwatch kernel that gives WRONG thresholds) never touches the
-    # product library or its objects: objects and the linked library go to build/variants/<hash>/, and only a process that
-    # sets PYLINAC_HIP_LIB to that path (see _lib.lib_path) loads it
-    tag = hashlib.sha256(" ".join(extra).encode()).hexdigest()[:12] if extra else ""
-    build_dir = BUILD if not extra else BUILD.parent / "variants" / tag
-    target = LIB if not extra else build_dir / "libpylinac_hip.so"
-    build_dir.mkdir(parents=True, exist_ok=True)
+    BUILD.mkdir(parents=True, exist_ok=True)
     headers = list(CSRC.glob("*.h")) + [PKG.parent / "include" / "pylinac_hip.h", Path(__file__)]
     jobs = []
     objs = []
     for src in sources():
-        obj = build_dir / (src.stem + ".o")
+        obj = BUILD / (src.stem + ".o")
         objs.append(obj)
         if force or _stale(obj, [src] + headers):
-            jobs.append([cc, *HIPCC_FLAGS, *EXTRA_FLAGS.get(src.name, []), *extra, "-c", str(src), "-o", str(obj)])
+            jobs.append([cc, *HIPCC_FLAGS, *EXTRA_FLAGS.get(src.name, []), "-c", str(src), "-o", str(obj)])
 
     def run(cmd):
         if verbose:
@@ -88,9 +80,9 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     if jobs:
         with ThreadPoolExecutor(max_workers=min(8, len(jobs))) as ex:
             list(ex.map(run, jobs))
-    if force or jobs or _stale(target, objs):
-        run([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(target), *map(str, objs)])
-    return target
+    if force or jobs or _stale(LIB, objs):
+        run([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(LIB), *map(str, objs)])
+    return LIB
 
 
 if __name__ == "__main__":

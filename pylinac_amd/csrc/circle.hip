@@ -169,9 +169,6 @@ circle_profile_combined_kernel(const T* __restrict__ stack, int h, int w, const 
 // r_lo / r_hi are the CALLER'S promise about |radii|.  A tap reads LDS only if its pixel lies inside a staged chord -- an
 // integer test against the row table -- and is fetched from the slices themselves otherwise (a radius outside the promise,
 // an annulus that does not fit the LDS handed in): a wrong promise costs time, never a sample.
-#ifndef PL_RING_VARIANT
-#define PL_RING_VARIANT 0   // stopwatch builds: 1 = staging only (no taps), 2 = row table + taps (no pixel staged: garbage samples)
-#endif
 constexpr int kRingThreads = 512, kRingRadLanes = 4, kRingSamples = kRingThreads / kRingRadLanes, kRingRadRegs = 8;
 
 template <typename T, int KPM>
@@ -269,7 +266,7 @@ circle_ring_kernel(const T* __restrict__ stack, int h, int w, const int64_t* __r
     if (threadIdx.x == 0) s_total = carry;
     __syncthreads();
     staged = s_total <= pix_cap;
-    if (staged && PL_RING_VARIANT != 2) {
+    if (staged) {
       // ---- the pixels: a wave takes FOUR rows per trip and issues their 4 x NS loads before the first is used (one row per trip
       // made the wave pay a memory round trip per row: r06m).  Lanes 0-31 walk the left chord, lanes 32-63 the right one (a
       // row with one chord: its second 32 pixels).  Loads are unconditional on clamped addresses; only the LDS store is guarded.
@@ -340,7 +337,7 @@ circle_ring_kernel(const T* __restrict__ stack, int h, int w, const int64_t* __r
   double myr[kRingRadRegs];
 #pragma unroll
   for (int m = 0; m < kRingRadRegs; ++m) myr[m] = rl + kRingRadLanes * m < nr ? rad[rl + kRingRadLanes * m] : 0.0;
-  const int n_passes = PL_RING_VARIANT == 1 ? 0 : (nsamp + kRingSamples - 1) / kRingSamples;
+  const int n_passes = (nsamp + kRingSamples - 1) / kRingSamples;
   int s = (int)(threadIdx.x / kRingRadLanes);
   s = s < nsamp ? s : nsamp - 1;
   double c = cosv[s], sn = sinv[s];

@@ -29,13 +29,6 @@
 #include "pl_common.h"
 #include "edge_exact.h"
 
-#ifndef PL_E32_AHEAD
-#define PL_E32_AHEAD 4      // rows a wave has in flight ahead of the one it works on
-#endif
-#ifndef PL_E32_WANT_FACTOR
-#define PL_E32_WANT_FACTOR 4
-#endif
-
 namespace {
 
 constexpr int kE32Threads = 256;
@@ -141,11 +134,12 @@ edge_stream32_kernel(const T* __restrict__ in, int h, int w, int strips, int seg
   f2 ra = unpack(ldo((unsigned)max(fr - 1, 0) * (unsigned)w)), rb = unpack(ldo((unsigned)fr * (unsigned)w));
   unsigned noff = min((unsigned)(fr + 1) * (unsigned)w, last_row);
   f2 rc = unpack(ldo(noff));
-  // PL_E32_AHEAD rows in flight per wave: with ONE (rounds up to r06z) a CU's 32 waves had 8 KB on their way, and the
+  // kE32Ahead rows in flight per wave: with ONE (rounds up to r06z) a CU's 32 waves had 8 KB on their way, and the
   // kernel's reads ran at what that buys against a microsecond and a half of latency (4.4 GB/s per CU: its 1.15 ms)
-  unsigned pend[PL_E32_AHEAD];
+  constexpr int kE32Ahead = 4;      // rows a wave has in flight ahead of the one it works on
+  unsigned pend[kE32Ahead];
 #pragma unroll
-  for (int j = 0; j < PL_E32_AHEAD; ++j) {
+  for (int j = 0; j < kE32Ahead; ++j) {
     noff = min(noff + (unsigned)w, last_row);
     pend[j] = ldo(noff);
   }
@@ -189,9 +183,9 @@ edge_stream32_kernel(const T* __restrict__ in, int h, int w, int strips, int seg
       const int vr = base + i;
       ra = rb; rb = rc; rc = unpack(pend[0]);
 #pragma unroll
-      for (int j = 0; j + 1 < PL_E32_AHEAD; ++j) pend[j] = pend[j + 1];
+      for (int j = 0; j + 1 < kE32Ahead; ++j) pend[j] = pend[j + 1];
       noff = min(noff + (unsigned)w, last_row);
-      pend[PL_E32_AHEAD - 1] = ldo(noff);                  // in flight for PL_E32_AHEAD steps
+      pend[kE32Ahead - 1] = ldo(noff);                     // in flight for kE32Ahead steps
       const f2 en = edge_row(ra, rb, rc);
       E[i] = en;
       if (__builtin_expect(vr > hm1, 0)) {                 // rows below the frame repeat the last edge row (wave-uniform)
@@ -327,7 +321,8 @@ int e32_launch(const T* in, int64_t n, int h, int w, const double* wts, int radi
                unsigned char* work, double* rawmax, double* dmin, double* dmax, int32_t* status, hipStream_t st) {
   const int hl = (radius + 2) / 2, outw = 2 * (PL_WAVE - 2 * hl);
   const int strips = (int)pl_cdiv(w, outw);
-  const int64_t want = (int64_t)PL_E32_WANT_FACTOR * pl_cu_count() * 32;   // waves the launch should at least have
+  constexpr int kE32WantFactor = 4;
+  const int64_t want = (int64_t)kE32WantFactor * pl_cu_count() * 32;   // waves the launch should at least have
   int segs = (int)pl_cdiv(want, n * strips);
   const int max_segs = (int)pl_cdiv(h, 32);
   if (segs > max_segs) segs = max_segs;

@@ -102,15 +102,9 @@ __global__ void minmax_init(double* mn, double* mx, int64_t n) {
   if (i < n) { mn[i] = __longlong_as_double(0x7ff0000000000000LL); mx[i] = __longlong_as_double((long long)0xfff0000000000000ULL); }
 }
 
-#ifndef PL_MINMAX_LOADS
-#define PL_MINMAX_LOADS 8
-#endif
-#ifndef PL_MINMAX_CHUNK_KB
-#define PL_MINMAX_CHUNK_KB 256
-#endif
-constexpr int kMinmaxLoads = PL_MINMAX_LOADS;                // 16-byte loads a lane keeps in flight
-constexpr int64_t kMinmaxChunkBytes = PL_MINMAX_CHUNK_KB * 1024;   // per workgroup (the elementwise kernels' 64 KiB blocks live too
-                                                                   // short for a pure reduction: 3.7 TB/s on 400 MB of frames)
+constexpr int kMinmaxLoads = 8;                              // 16-byte loads a lane keeps in flight
+constexpr int64_t kMinmaxChunkBytes = 256 * 1024;            // per workgroup (the elementwise kernels' 64 KiB blocks live too
+                                                             // short for a pure reduction: 3.7 TB/s on 400 MB of frames)
 template <typename T>
 __global__ void __launch_bounds__(kThreads)
 minmax_kernel(const T* __restrict__ in, int64_t count, int64_t chunk, int bpf, double* mn, double* mx) {

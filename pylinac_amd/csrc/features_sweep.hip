@@ -25,17 +25,6 @@
 // Results are identical to features.hip's level-by-level path (tests run both on the same windows).
 #include "pl_common.h"
 
-// Phase stopwatch (-DPL_SWEEP_TIMING, development builds only): per-workgroup s_memtime totals of the level loop's phases.
-#ifndef PL_SWEEP_TIMING
-#define PL_SWEEP_TIMING 0
-#endif
-#if PL_SWEEP_TIMING
-__device__ unsigned long long pl_sweep_dbg[8];
-#define SW_STAMP(k) do { if (tid == 0) { const long long t_ = clock64(); tacc[k] += t_ - tlast; tlast = t_; } } while (0)
-#else
-#define SW_STAMP(k) do { } while (0)
-#endif
-
 namespace {
 
 constexpr int kSwThreads = 256;
@@ -213,14 +202,10 @@ bb_sweep_kernel(const double* __restrict__ sample, const SweepSrc src, int h, in
   __syncthreads();
   const unsigned long long level_used = s_used;
 
-#if PL_SWEEP_TIMING
-  long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = clock64();
-#endif
   for (int level = 0; level < prm.nlevels; ++level) {
     // (with min_separation == 0 the reference's duplicate test -- distance STRICTLY below the separation -- never fires, and a
     // repeated mask appends the same centroids again until max_number is reached: every level runs then)
     if (level > 0 && prm.min_sep_px > 0 && !((level_used >> level) & 1ull)) continue;
-    SW_STAMP(7);
     // ---- A. the row's foreground as a 160-bit mask (lane = row): four level-map bytes per LDS read, "byte > level" for all
     // four at once (bytes <= 64: adding 127 - level sets bit 7 exactly where the byte exceeds the level), the four flags
     // gathered into a nibble.  Runs start where a set bit follows a clear one: popcount.  (Round 2 walked the row byte by
@@ -339,7 +324,6 @@ bb_sweep_kernel(const double* __restrict__ sample, const SweepSrc src, int h, in
       if (slot < 32) s_cand[slot] = id;
     }
     __syncthreads();
-    SW_STAMP(0);                                              // runs, merge, flatten, region table, candidate screen
     int ncand = s_ncand;
     if (ncand > 32) { ncand = 32; if (tid == 0) s_status = 2; }
     if (tid == 0)                                             // label order = raster order of the first pixel = root id order
@@ -365,7 +349,6 @@ bb_sweep_kernel(const double* __restrict__ sample, const SweepSrc src, int h, in
         }
       }
       __syncthreads();
-      SW_STAMP(1);                                            // crop mask
       // ---- filled_area: non-region pixels reachable (8-conn) from the crop border are NOT holes
       for (int e = tid; e < cpx; e += kSwThreads) {
         const int r = e / cw, c = e % cw;
@@ -392,7 +375,6 @@ bb_sweep_kernel(const double* __restrict__ sample, const SweepSrc src, int h, in
         }
         if (!__syncthreads_or(changed)) break;
       }
-      SW_STAMP(2);                                            // flood fill
       if (tid < 4) s_cnt[tid] = 0;
       __syncthreads();
       // ---- holes, perimeter codes, weighted moments
@@ -422,12 +404,11 @@ bb_sweep_kernel(const double* __restrict__ sample, const SweepSrc src, int h, in
         atomicAdd(&s_cnt[0], holes); atomicAdd(&s_cnt[1], n1); atomicAdd(&s_cnt[2], n2); atomicAdd(&s_cnt[3], n3);
         s_red[0][wv] = w0; s_red[1][wv] = wr; s_red[2][wv] = wc;
       }
-      SW_STAMP(3);                                            // holes, perimeter, moments
       // ---- convex hull of the pixels' mid-edge points (the "diamond" hull skimage's convex_hull_image builds).
       // Only the row-extreme pixels matter, and of their points only, for every doubled abscissa X = 2 r - 1 .. 2 r + 1, the
       // lowest and the highest ordinate: X even (= 2 r): 2 cl - 1 and 2 cr + 1; X odd (between rows r and r + 1): min of the two
       // rows' 2 cl, max of their 2 cr.  That is at most 2 (2 ch + 1) points ALREADY SORTED by X.  Round 2 sorted eight points per
-      // row by insertion and ran Andrew's chains on ONE lane: 73 % of this kernel's time (phase stopwatch, -DPL_SWEEP_TIMING).
+      // row by insertion and ran Andrew's chains on ONE lane: 73 % of this kernel's time (phase stopwatch).
       // Now one wave prunes each chain in parallel: a point whose turn (previous alive, itself, next alive) is not strictly
       // counter-clockwise lies on or inside the chord of two other points and is no hull vertex -- all such points go at once,
       // until none is left: the same strictly convex polygon as the sequential chains, a handful of rounds.
@@ -533,7 +514,6 @@ bb_sweep_kernel(const double* __restrict__ sample, const SweepSrc src, int h, in
       }
       }
       __syncthreads();
-      SW_STAMP(4);                                            // hull
       const int nh = s_nh;
       int inside = 0;
       for (int e = tid; e < cpx; e += kSwThreads) {
@@ -548,7 +528,6 @@ bb_sweep_kernel(const double* __restrict__ sample, const SweepSrc src, int h, in
       inside = pl_wave_reduce(inside, addi);
       if (lane == 0) atomicAdd(&s_inside, inside);
       __syncthreads();
-      SW_STAMP(5);                                            // pixels inside the hull
       // ---- predicates (pylinac/metrics/features.py) and output
       if (tid == 0) {
         const double filled = area + (double)s_cnt[0];
@@ -590,9 +569,6 @@ bb_sweep_kernel(const double* __restrict__ sample, const SweepSrc src, int h, in
     if (s_nout >= prm.max_number) break;                     // while ... len(total_features) < max_number
   }
   __syncthreads();
-#if PL_SWEEP_TIMING
-  if (tid == 0) for (int k = 0; k < 8; ++k) atomicAdd(&pl_sweep_dbg[k], (unsigned long long)tacc[k]);
-#endif
   if (tid == 0) {
     out_count[img] = s_nout;
     out_level[img] = s_first_level;
@@ -689,9 +665,3 @@ extern "C" int pl_features_sweep_u16(const uint16_t* d_frames, int64_t n, int fr
   return sweep_launch(nullptr, src, n, h, w, dpmm, radius_mm, tol_mm, min_sep_px, max_number, h_cutoffs, nlevels, d_count,
                       d_xy, d_level, d_status, stream, "pl_features_sweep_u16");
 }
-
-#if PL_SWEEP_TIMING
-extern "C" int pl_debug_sweep_timing(unsigned long long* h_out) {
-  return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(pl_sweep_dbg), sizeof(pl_sweep_dbg)) == hipSuccess ? 0 : 1;
-}
-#endif

@@ -42,13 +42,6 @@
 
 #include "pl_common.h"
 
-// Timing-attribution switches for scripts/ubench/g2d_variants.hip ONLY (results become wrong): bit 0 drops the MFMAs,
-// bit 1 the integer recombination, bit 2 the global loads, bit 3 the per-step barrier, bit 4 the global stores, bit 5 the plane
-// split + LDS writes of the input, bit 6 the LDS writes of the axis-0 plane, bit 7 the LDS operand reads, bit 8 the two level-1 MFMAs and every fix-up.
-#ifndef PL_G2D_VARIANT
-#define PL_G2D_VARIANT 0
-#endif
-
 namespace {
 
 constexpr int kMmHalo = 24;                 // window start = first output - 24: 16-byte aligned, covers RAD <= 24
@@ -173,7 +166,6 @@ __device__ __forceinline__ MmConst mm_const(const MmParams& P) {
 template <bool IMG_IS_A>
 __device__ __forceinline__ MmAcc mm_tile(v4i img_lo, v4i img_hi, const v4i (&w)[kMmDigits], const MmConst& K) {
   auto mm = [&](v4i img, v4i band, v4i c) -> v4i {
-    if (PL_G2D_VARIANT & 1) return c;              // no matrix instruction
     return IMG_IS_A ? __builtin_amdgcn_mfma_i32_16x16x64_i8(img, band, c, 0, 0, 0)
                     : __builtin_amdgcn_mfma_i32_16x16x64_i8(band, img, c, 0, 0, 0);
   };
@@ -197,20 +189,14 @@ template <bool IMG_IS_A, int NT>
 __device__ __forceinline__ void mm_tiles(const v4i (&lo)[NT], const v4i (&hi)[NT], const v4i (&w)[kMmDigits], const MmConst& K,
                                          MmAcc (&r)[NT]) {
   auto mm = [&](v4i img, v4i band, v4i c) -> v4i {
-    if (PL_G2D_VARIANT & 1) return c;              // no matrix instruction
     return IMG_IS_A ? __builtin_amdgcn_mfma_i32_16x16x64_i8(img, band, c, 0, 0, 0)
                     : __builtin_amdgcn_mfma_i32_16x16x64_i8(band, img, c, 0, 0, 0);
   };
   v4i t[NT], t3[NT], t4[NT];
-  if (PL_G2D_VARIANT & 256) {                      // stopwatch only: what would a 7-MFMA tile (no level 1) cost?
-#pragma unroll
-    for (int i = 0; i < NT; ++i) t[i] = K.c1 + lo[i];
-  } else {
 #pragma unroll
   for (int i = 0; i < NT; ++i) t[i] = mm(lo[i], w[1], K.c1);                  // level 1
 #pragma unroll
   for (int i = 0; i < NT; ++i) t[i] = mm(hi[i], w[0], t[i]);
-  }
 #pragma unroll
   for (int i = 0; i < NT; ++i) t[i] = mm(lo[i], w[2], t[i] >> 8);             // level 2
 #pragma unroll
@@ -265,10 +251,6 @@ struct FQuad { uint2 r[4]; };                     // 4 rows x 4 columns of raw 1
 
 // a tile operand: 16 bytes of one plane
 __device__ __forceinline__ uint4 f_ldsq(const unsigned char* p) {
-  if (PL_G2D_VARIANT & 128) {
-    const unsigned a = (unsigned)(uintptr_t)p;
-    return uint4{a, a * 3u, a * 5u, a * 7u};
-  }
   return *reinterpret_cast<const uint4*>(p);
 }
 
@@ -291,15 +273,6 @@ __device__ __forceinline__ bool mm_wave_flat(const uint4& lo, const uint4& hi) {
 // four outputs of a lane, branch-free: packed results and ONE flag (some output of the four is undecided)
 template <bool SIGNED>
 __device__ __forceinline__ uint2 mm_finish_flag(const MmAcc& r, bool& bad) {
-  if (PL_G2D_VARIANT & 256) {                      // 7-MFMA stopwatch: results are garbage, nothing is undecided
-    bad = false;
-    return uint2{__builtin_amdgcn_perm((unsigned)r.v[1], (unsigned)r.v[0], 0x05040100u) ^ (unsigned)r.z[0],
-                 __builtin_amdgcn_perm((unsigned)r.v[3], (unsigned)r.v[2], 0x05040100u) ^ (unsigned)r.z[3]};
-  }
-  if (PL_G2D_VARIANT & 2) {
-    bad = false;
-    return uint2{(unsigned)(r.v[0] ^ r.z[1]), (unsigned)(r.v[2] ^ r.z[3])};
-  }
   unsigned v[4], z[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -334,17 +307,6 @@ __device__ __forceinline__ uint2 mm_finish_flag(const MmAcc& r, bool& bad) {
 // each to waves 5 .. 7 (which load nothing); the 16 axis-1 tiles go pairwise (2 v, 2 v + 1: the permlane16_swap partners).
 // One segment per strip where the frame allows: 256 x 1024 x 1024 -> 1024 workgroups = exactly two rounds of the 512
 // resident ones, 64 steps after a four-group prologue (the 4-wave kernel: 3072 workgroups, four rounds, 22 steps each).
-// Phase stopwatch for scripts/ubench/gauss2d_variants.hip ONLY (-DPL_G2D_TIMING): per wave, s_memtime totals of the four
-// phases of a step (W + load issue, axis 0, barrier wait, axis 1) -> g2d_dbg[workgroup][wave][4].
-#ifndef PL_G2D_TIMING
-#define PL_G2D_TIMING 0
-#endif
-#if PL_G2D_TIMING
-__device__ unsigned long long g2d_dbg[4096 * 8 * 4];
-#define PL_G2D_STAMP(k) do { const long long t_ = clock64(); tacc[k] += t_ - tlast; tlast = t_; } while (0)
-#else
-#define PL_G2D_STAMP(k) do { } while (0)
-#endif
 constexpr int kGThreads = 512;
 constexpr int kGWaves = kGThreads / PL_WAVE;
 constexpr int kGSlots = 5;
@@ -463,16 +425,6 @@ gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int stri
   const int lane_cell = f_cell(j);                 // cell of column 16 t + j, less the tile's 64 t bytes
   int slot_g = g;                                  // slot of row group s + g
   int wslot = 4;                                   // slot that receives group s + 4
-#if PL_G2D_TIMING
-  long long tacc[4] = {0, 0, 0, 0}, tlast = clock64();
-#endif
-#ifdef PL_G2D_EXP
-  // experiments (stopwatch builds only): de-phase the workgroups that share a CU
-  if (PL_G2D_EXP & 4) { if ((blockIdx.x >> 8) & 1) { __builtin_amdgcn_s_sleep(50); } }
-  if (PL_G2D_EXP & 8) { if (blockIdx.x & 1) { __builtin_amdgcn_s_sleep(50); } }
-  if (PL_G2D_EXP & 16) { if ((blockIdx.x >> 3) & 1) { __builtin_amdgcn_s_sleep(50); } }
-  if (PL_G2D_EXP & 32) { if ((blockIdx.x >> 9) & 1) { __builtin_amdgcn_s_sleep(50); } }
-#endif
   auto step = [&](int s) {
     const int vb = (s & 1) * kFPlane;              // this step's axis-0 result plane
     const int lrow = 16 * s + j;                   // the lane's output row inside the segment, both passes
@@ -541,14 +493,11 @@ gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int stri
       // tiles 0 .. 9: waves 0 .. 4 (w, w + 5); tiles 10 .. 18: waves 5 .. 7 (10 + (w - 5), + 3, + 6)
       if (wave < 5) run(std::integral_constant<int, 2>{}, wave, 5); else run(std::integral_constant<int, 3>{}, 5 + wave, 3);
     }
-    PL_G2D_STAMP(1);
     // W after the axis-0 tiles: the group loaded during the previous step (s + 4) has had a whole step to arrive, and the
     // output stores of the previous axis-1 pass, which the in-order vmcnt makes this wait for as well, an axis-0 pass
     store_quad(wslot, nxt);
     load_quad(s + 5, nxt);
-    PL_G2D_STAMP(0);
     __syncthreads();
-    PL_G2D_STAMP(2);
 
     // ---- axis 1: Toeplitz (M = output column) x image (N = row j): lane (j, g) gets columns 16 t + 4 g .. + 3 of row j
     {
@@ -628,14 +577,9 @@ gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int stri
     }
     slot_g = slot_g == kGSlots - 1 ? 0 : slot_g + 1;
     wslot = wslot == kGSlots - 1 ? 0 : wslot + 1;
-    PL_G2D_STAMP(3);
   };
 #pragma unroll 1
   for (int s = 0; s < nsteps; ++s) step(s);
-#if PL_G2D_TIMING
-  if (lane == 0 && blockIdx.x < 4096)
-    for (int k = 0; k < 4; ++k) g2d_dbg[(blockIdx.x * 8 + wave) * 4 + k] = (unsigned long long)tacc[k];
-#endif
 }
 
 

@@ -25,9 +25,7 @@
 #include "median3_rows.h"
 
 // rows the fused median + Otsu kernel keeps in flight per lane (1024 threads: 128 VGPRs)
-#ifndef PL_OTSU_AHEAD
-#define PL_OTSU_AHEAD 2
-#endif
+constexpr int kOtsuAhead = 2;
 
 namespace {
 
@@ -263,9 +261,6 @@ otsu_kernel(const uint32_t* __restrict__ hist, int bias, int32_t* __restrict__ t
 // row, centred in the window (filtered frames are smooth: the sample misses the true extrema by a few counts, the
 // slack on either side is hundreds to thousands).  A pixel outside the window, or a range wider than the window,
 // sets flag[frame] = 1: the frame is then left to the two-kernel path, launched right behind and gated per frame by that flag.
-#ifndef PL_OTSU_VARIANT
-#define PL_OTSU_VARIANT 0
-#endif
 constexpr int kWinBins = 38912;   // 152 KiB
 struct OtsuScratch {
   Pair wave_tot[kHistThreads / 64];
@@ -365,9 +360,6 @@ otsu16_window_kernel(const unsigned short* __restrict__ in, int64_t count, int h
     constexpr int kRows = 32;                        // rows per item: two halo rows are re-read per item
     constexpr int kSBias = ((T)-1 < (T)0) ? 32768 : 0;          // median (sign-extended for int16) -> key of the biased domain
     const unsigned kbase4 = 4u * (unsigned)(kSBias - klo);
-#if PL_OTSU_VARIANT & 1
-    unsigned dummy = 0;
-#endif
     const int col_waves = (w / 8 + PL_WAVE - 1) / PL_WAVE, row_groups = (h + kRows - 1) / kRows;
     const int rg_lo = (int)((int64_t)row_groups * part / parts), rg_hi = (int)((int64_t)row_groups * (part + 1) / parts);
     for (int item = rg_lo * col_waves + __builtin_amdgcn_readfirstlane(wv); item < col_waves * rg_hi; item += kHistThreads / 64) {   // scalar
@@ -379,7 +371,7 @@ otsu16_window_kernel(const unsigned short* __restrict__ in, int64_t count, int h
       const int first_on = __builtin_ctzll(act);
       const unsigned cap4 = on ? 4u * (unsigned)range : 0u;      // lanes beyond the frame add 0 to bin 0
       const unsigned inc = on ? 1u : 0u;
-      pl_median3_rows<T, kRows, PL_OTSU_AHEAD>(reinterpret_cast<const T*>(src), h, w, c0, lane, (item / col_waves) * kRows,
+      pl_median3_rows<T, kRows, kOtsuAhead>(reinterpret_cast<const T*>(src), h, w, c0, lane, (item / col_waves) * kRows,
                              [&](int, const int (&m)[8]) {
         // one value in the whole wave (saturated / constant neighbourhoods): ONE atomic of 8 x the lane count -- 512 atomics
         // on one address would serialise
@@ -403,17 +395,10 @@ otsu16_window_kernel(const unsigned short* __restrict__ in, int64_t count, int h
         for (int k = 0; k < 8; ++k) {
           const unsigned b4 = ((unsigned)m[k] << 2) + kbase4;
           const unsigned a4 = b4 < cap4 ? b4 : cap4;
-#if PL_OTSU_VARIANT & 1    // stopwatch only: everything but the LDS atomics
-          dummy += a4;
-#else
           pl_lds_add_abs(a4, inc);
-#endif
         }
       });
     }
-#if PL_OTSU_VARIANT & 1
-    if (dummy == 0x12345678u) bins[0] = 1;
-#endif
   } else if ((reinterpret_cast<uintptr_t>(src) & 15) == 0) {
     const int64_t nvec = count / 8;
     const uint4* vsrc = reinterpret_cast<const uint4*>(src);
@@ -496,11 +481,7 @@ otsu16_window_kernel(const unsigned short* __restrict__ in, int64_t count, int h
   // and first-index arg-max as otsu_kernel
   // an ODD number of bins per lane: lane t's j-th bin sits in bank (per * t + j) mod 32, and with the even 38 of a full window
   // the 64 lanes of a read met in 16 banks (four-way conflicts on each of the 2 x 38 reads); 39 spreads them over all 32
-#ifdef PL_OTSU_EVEN_PER
-  const int per = (range + kHistThreads - 1) / kHistThreads;
-#else
   const int per = ((range + kHistThreads - 1) / kHistThreads) | 1;
-#endif
   const int b0 = threadIdx.x * per;
   const int b1 = b0 + per < range ? b0 + per : range;
   Pair mine = {0, 0};
@@ -605,11 +586,7 @@ __device__ __forceinline__ void full_tally_pass(const unsigned short* __restrict
     // on one dword serialise in the LDS atomic unit)
     const unsigned sh = (key >> 15) << 4, at = key & 0x7fffu;
     if (!GUARD) {                // four vector instructions and the atomic; the bins start the workgroup's LDS (kernel's test)
-#if PL_OTSU_VARIANT & 1            // stopwatch only: everything but the LDS atomics
-      asm volatile("" ::"v"((key << 2) & 0x1fffcu), "v"(n * (1u + ((key >> 15) & 1u) * 0xffffu)));
-#else
       pl_lds_add_abs((key << 2) & 0x1fffcu, n * (1u + ((key >> 15) & 1u) * 0xffffu));
-#endif
       return;
     }
     const unsigned old = atomicAdd(&bins[at], n << sh);
@@ -645,7 +622,7 @@ __device__ __forceinline__ void full_tally_pass(const unsigned short* __restrict
       const unsigned long long act = __ballot(on);
       if (act == 0ull) continue;
       const int first_on = __builtin_ctzll(act);
-      pl_median3_rows<T, kRows, PL_OTSU_AHEAD>(reinterpret_cast<const T*>(src), h, w, c0, lane, (item / col_waves) * kRows,
+      pl_median3_rows<T, kRows, kOtsuAhead>(reinterpret_cast<const T*>(src), h, w, c0, lane, (item / col_waves) * kRows,
                              [&](int, const int (&m)[8]) {
         // one value in the whole wave (saturated / constant neighbourhoods): one add of the wave's count
         unsigned spread = 0;
@@ -674,9 +651,7 @@ otsu16_full_kernel(const unsigned short* __restrict__ in, int64_t count, int h, 
   extern __shared__ __attribute__((aligned(16))) unsigned bins[];  // 32 768 dwords = 65 536 fields, then FullScratch
   FullScratch& scr = *reinterpret_cast<FullScratch*>(reinterpret_cast<unsigned char*>(bins) + kFullBinsBytes);
   const int64_t frame = blockIdx.x;
-#ifndef PL_OTSU_FULL_ALWAYS
   if (flag[frame] == 0) return;                              // the window kernel finished this frame
-#endif
   const unsigned short* src = in + frame * count;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   auto clear = [&]() {
@@ -829,14 +804,6 @@ order_stats_kernel(const uint32_t* __restrict__ hist, int bias, const int64_t* _
 // unchanged (1.51); at 256 frames, one workgroup per CU either way, the small windows are 4 % slower: taken only for batches
 // of more frames than the chip has CUs.
 constexpr int kTwBinsWide = 19456, kTwBinsWl = 9728;
-#ifndef PL_TW_TIMING
-#define PL_TW_TIMING 0   // 1: thread 0 leaves wall_clock64() stamps of the phases in bins 65520.. of the frame's table (timing builds only)
-#endif
-#if PL_TW_TIMING
-#define TW_STAMP(k) do { __syncthreads(); if (threadIdx.x == 0) tw_stamp[k] = wall_clock64(); } while (0)
-#else
-#define TW_STAMP(k) do { } while (0)
-#endif
 struct TwScratch { int s_lo[kHistThreads / 64], s_hi[kHistThreads / 64]; };
 constexpr int tw_scratch_at(int bins) { return (2 * bins + 1 + PL_WAVE + 3) / 4 * 16; }   // two windows, the spare bin, one dummy bin per lane
 constexpr size_t tw_lds(int bins) { return tw_scratch_at(bins) + sizeof(TwScratch); }
@@ -857,10 +824,6 @@ hist16_two_window_kernel(const unsigned short* __restrict__ in, int64_t count, u
   const int64_t nvec = vec ? count / 8 : 0;
   const uint4* vsrc = reinterpret_cast<const uint4*>(src);
 
-#if PL_TW_TIMING
-  unsigned long long tw_stamp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-  TW_STAMP(0);
   for (int i = threadIdx.x; i < 2 * kTwBins; i += kHistThreads) bins[i] = 0;
   if (edge_min) {
     // min / max over the four `ews`-wide edge strips of the eh x ew frame (WLBaseImage._clean_edges' edge test,
@@ -906,7 +869,6 @@ hist16_two_window_kernel(const unsigned short* __restrict__ in, int64_t count, u
     }
     __syncthreads();                                                  // (the scratch is used again for the sample's extrema)
   }
-  TW_STAMP(1);
   // tile maxima (pl_hist16_tiles): tile t = pixels [512 t, 512 t + 512) = the 64 vectors ONE wave load of the main loop
   // fetches; its largest key (biased domain) lets a later pass skip every tile that cannot hold a pixel above its
   // threshold (pl_field_cax_tiles).  Tiles the main loop does not cover keep 0xffff ("look inside").
@@ -940,7 +902,6 @@ hist16_two_window_kernel(const unsigned short* __restrict__ in, int64_t count, u
   __syncthreads();
   for (int k = 0; k < kHistThreads / 64; ++k) { mn = scr.s_lo[k] < mn ? scr.s_lo[k] : mn; mx = scr.s_hi[k] > mx ? scr.s_hi[k] : mx; }
   if (mx < mn) { mn = 0; mx = 0; }
-  TW_STAMP(2);
   // window bases (biased key domain): contiguous [w0, w0 + 2 W) around a narrow range, else one window at each end
   int w0, w1;
   if (mx - mn + 1 <= 2 * kTwBins) {
@@ -962,7 +923,6 @@ hist16_two_window_kernel(const unsigned short* __restrict__ in, int64_t count, u
     if (!inside) reinterpret_cast<uint4*>(row)[i] = uint4{0u, 0u, 0u, 0u};
   }
   __syncthreads();                                   // the zeroed table is in place before any global atomic
-  TW_STAMP(3);
 
   unsigned hot = 0;                                  // this lane's pixels that equalled the wave's guess since the last flush
   unsigned guess = 0xffffffffu;                      // wave-uniform key (biased domain), none yet
@@ -1060,7 +1020,6 @@ hist16_two_window_kernel(const unsigned short* __restrict__ in, int64_t count, u
   for (int64_t i = nvec * 8 + threadIdx.x; i < count; i += kHistThreads) tally1(src[i]);
   flush();
   __syncthreads();
-  TW_STAMP(4);
   if (ranks) {
     // pl_hist16_wl: the order statistics are taken HERE, from the windows while they are still in LDS (order_stats_kernel's
     // selection: thread t owns bins [64 t, 64 t + 64), exclusive scan of the counts, the bin where the running count passes
@@ -1114,11 +1073,9 @@ hist16_two_window_kernel(const unsigned short* __restrict__ in, int64_t count, u
         for (int k = 0; k < 32; ++k) both += val[k];
       }
     }
-    TW_STAMP(5);
     Pair mine = {both, 0};
     Pair total;
     const Pair ex = block_exclusive_scan(mine, &total, wave_tot);
-    TW_STAMP(6);
     const int bias = (int)flip;                                       // 0x8000 for int16 keys
     auto clamped = [&](int q) {
       long long r = ranks[q];
@@ -1159,11 +1116,6 @@ hist16_two_window_kernel(const unsigned short* __restrict__ in, int64_t count, u
         before += here;
       }
     }
-#if PL_TW_TIMING
-    TW_STAMP(7);
-    if (threadIdx.x == 0)
-      for (int k = 0; k < 8; ++k) row[65520 + k] = (uint32_t)(tw_stamp[k] - tw_stamp[0]);   // 10 ns units (100 MHz)
-#endif
     return;
   }
   // the windows go out with plain stores: no global atomic ever touched a bin inside a window
@@ -1318,12 +1270,8 @@ int otsu16_launch(const void* in, void* scratch, int dtype, int64_t n, int64_t c
     if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, (size_t)n * sizeof(int32_t), st);
     if (e != hipSuccess) { pl_set_error("%s: memset: %s", who, hipGetErrorString(e)); return PL_ERR_HIP; }
   }
-#ifdef PL_OTSU_FULL_ALWAYS                                    // development variant: every frame through the full-range kernel
-  (void)hipMemsetAsync(d_flag, 0, (size_t)n * sizeof(int32_t), st);
-#else
   hipLaunchKernelGGL((otsu16_window_kernel<T, MED3>), dim3((unsigned)(n * parts)), dim3(kHistThreads), lds, st,
                      (const unsigned short*)in, count, h, w, flip, bias, d_lo, d_hi, d_thr, d_min, d_max, d_flag, parts, d_hist);
-#endif
   // frames too wide for the window: the full-range kernel (packed 16-bit counters), every workgroup gated by d_flag; the
   // medians are computed on the fly again for exactly those frames.  (Round 3: gated median plane + two-part histogram +
   // scan, 2.2 x the window kernel's time on a stretched batch.)  Frames beyond 2^26 pixels keep the table path.

@@ -11,9 +11,6 @@
 // Needs w % 8 == 0, 16-byte aligned rows, h > 1.
 #pragma once
 // (included after pl_common.h by every user)
-#ifndef PL_MEDIAN_ROLL
-#define PL_MEDIAN_ROLL 1
-#endif
 
 // consume(r, m): m[j] = median of column c0 + j of row r (the value itself: sign-extended for int16 frames).
 // AHEAD rows are in flight as raw 16-byte loads before their turn (the consumers that run few waves per CU -- one workgroup
@@ -78,8 +75,7 @@ __device__ __forceinline__ void pl_median3_rows(const T* __restrict__ f, int h, 
   Raw ring[AHEAD];
 #pragma unroll
   for (int k = 0; k < AHEAD; ++k) ring[k] = fetch(r0 - 1 + k);
-#if PL_MEDIAN_ROLL
-  // Rolled walk (the default; -DPL_MEDIAN_ROLL=0 builds the straight-line one): the body below is kChunk rows -- a multiple of 3
+  // Rolled walk: the body below is kChunk rows -- a multiple of 3
   // (the sorted-triple slots) and of AHEAD (the load ring), so every slot index in it is a compile-time constant -- inside a real
   // loop; the ROWS % kChunk rows that remain follow unrolled.  The straight-line form of 34 rows is 40 KB of code per
   // instantiation, and that is what made the two median stages box-dependent: on the evidence boxes where they ran 1.3x slower
@@ -107,16 +103,6 @@ __device__ __forceinline__ void pl_median3_rows(const T* __restrict__ f, int h, 
     step(k, k % AHEAD, k % 3);
     emit(k);
   }
-#else
-#pragma unroll
-  for (int k = 0; k < ROWS + 2; ++k) {              // walk row k = frame row r0 - 1 + k
-    const Raw cur = ring[k % AHEAD];
-    if (k + AHEAD < ROWS + 2) ring[k % AHEAD] = fetch(r0 - 1 + k + AHEAD);
-    digest(cur, k % 3);
-    if (k < 2) continue;
-    emit(k);
-  }
-#endif
 }
 
 // the 16-bit patterns of two values in one dword (low half = a)

@@ -29,9 +29,6 @@
 
 namespace {
 
-#ifndef PL_PF_VARIANT
-#define PL_PF_VARIANT 0         // 1 / 2 / 3: stopwatch builds that skip a stage of pf_windows_kernel (WRONG results; scripts/)
-#endif
 constexpr int kThreads = 256;
 constexpr int kMaxRows = 48;    // window rows (leaf width in pixels) of the launch configuration every EPID leaf fits
 constexpr int kMaxRowsTall = 64;  // window rows of the tall-leaf instantiations (film scans, fine panels): one lane per row
@@ -59,12 +56,8 @@ scaled_colmean_kernel(const unsigned short* __restrict__ in, int h, int w, int c
 // Round 1-3's one-column lanes reached 1 TB/s (a dependent float64 division per row and 128-byte wave loads).
 // COLS = 2 (round 4): twice the waves (256 frames x 1024 columns are 1024 waves at four columns per lane -- ONE per SIMD, which
 // then alternates between waiting for its loads and dividing) with twice the rows in flight.
-#ifndef PL_COLMEAN_COLS
-#define PL_COLMEAN_COLS 2
-#endif
-#ifndef PL_COLMEAN_ROWS
-#define PL_COLMEAN_ROWS 32
-#endif
+constexpr int kColmeanCols = 2;
+constexpr int kColmeanRows = 32;
 template <int COLS, int U>
 __global__ void __launch_bounds__(kThreads)
 scaled_colmeanv_kernel(const unsigned short* __restrict__ in, int h, int w, int64_t total_groups,
@@ -522,9 +515,6 @@ pf_windows_kernel(const T* __restrict__ in, int h, int w, const double* __restri
   }
   }
   if (!decided) {
-#if PL_PF_VARIANT == 1                                     // stopwatch: no deviation stage (wrong edge test)
-  if (lane < nrows) s_std_w[lane] = 1.0;
-#else
   if (lr) {
     // LEFT_RIGHT: np.std(window, axis=0) reduces over the window's ROWS (the travel direction), which numpy adds up one row
     // after the other -- no pairwise blocks on a non-contiguous reduction axis: a plain left-to-right sum per leaf pixel
@@ -565,7 +555,6 @@ pf_windows_kernel(const T* __restrict__ in, int h, int w, const double* __restri
       if (act && j == 0) s_std_w[r] = sqrt(ss / (double)ncols);
     }
   }
-#endif
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
   // max(std) < edge_threshold * np.median(std): lane a ranks std[a] (nrows <= MAXR <= 64 lanes)
@@ -599,9 +588,6 @@ pf_windows_kernel(const T* __restrict__ in, int h, int w, const double* __restri
     if (c >= ncols) continue;
     const int k_hi = nrows / 2, k_lo = (nrows & 1) ? k_hi : k_hi - 1;
     K v_lo = 0, v_hi = 0;
-#if PL_PF_VARIANT == 2                                     // stopwatch: no column median (row 0 instead)
-    v_lo = v_hi = sw[c];
-#else
     if (nrows <= 32) {                               // wave-uniform; every leaf of the Millennium / HD / Agility banks at EPID scale
       // A sorting network on the column in registers.  The column is padded to N values with floor((N - n) / 2) values below
       // every pixel and the rest above: the middle order statistics then sit at the FIXED positions N/2 - 1 and N/2 (n even)
@@ -625,7 +611,6 @@ pf_windows_kernel(const T* __restrict__ in, int h, int w, const double* __restri
         if (rank == k_hi) v_hi = va;
       }
     }
-#endif
     if constexpr (kF64) {
       pvr[slot] = (nrows & 1) ? v_hi : (v_lo + v_hi) / 2.0;
     } else {
@@ -658,12 +643,7 @@ pf_windows_kernel(const T* __restrict__ in, int h, int w, const double* __restri
   // 322-327: find_peaks(fwxm_height, max_number = 1), left_ips / right_ips of the most prominent peak) -- rounds 1-3 wrote the
   // profile to a [windows][128] float64 table (0.5 GB per 512 frames) for a second launch to read
   double c_pos = qnan, l_pos = qnan, r_pos = qnan;
-#if PL_PF_VARIANT == 3                                     // stopwatch: no FWXM search
-  if (status == 0) c_pos = l_pos = r_pos = p0 + p1;
-  if (false) {
-#else
   if (status == 0) {                                       // wave-uniform
-#endif
     pl_wave_sync();                                        // every lane is done with the window pixels: the bytes change hands
     double* s_prof = reinterpret_cast<double*>(wave_lds);
     if (has0) s_prof[lane] = p0;
@@ -702,9 +682,9 @@ extern "C" int pl_scaled_colmean(const uint16_t* in, int64_t n, int h, int w, co
   const int col_tiles = (int)pl_cdiv(w, kThreads);
   PL_REQUIRE(n * col_tiles <= 0x7fffffffLL, "batch too large");
   if ((w & 3) == 0 && (reinterpret_cast<uintptr_t>(in) & 7) == 0) {
-    const int64_t groups = n * (int64_t)(w / PL_COLMEAN_COLS);
+    const int64_t groups = n * (int64_t)(w / kColmeanCols);
     PL_REQUIRE(pl_cdiv(groups, kThreads) <= 0x7fffffffLL, "batch too large");
-    hipLaunchKernelGGL((scaled_colmeanv_kernel<PL_COLMEAN_COLS, PL_COLMEAN_ROWS>), dim3((unsigned)pl_cdiv(groups, kThreads)),
+    hipLaunchKernelGGL((scaled_colmeanv_kernel<kColmeanCols, kColmeanRows>), dim3((unsigned)pl_cdiv(groups, kThreads)),
                        dim3(kThreads), 0, (hipStream_t)stream, in, h, w, groups, d_sub, d_div, d_out);
     return pl_check_launch("pl_scaled_colmean");
   }

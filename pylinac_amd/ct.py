@@ -22,7 +22,6 @@ against scikit-image on the golden slices.
 """
 from __future__ import annotations
 
-import os
 import warnings
 
 import numpy as np
@@ -31,8 +30,8 @@ import torch
 from . import ops, regionprops as _rp
 
 CATPHAN_RADIUS_MM = 101  # pylinac/ct.py: CatPhanBase.catphan_radius_mm
-EDGE_PLANE32 = os.environ.get("PL_EDGE_PLANE32", "1") != "0"   # the localisation's edge image from pl_edge_plane32 (0: the exact
-                                                             # float64 kernel -- an A/B knob; results are identical)
+# the localisation's edge image from pl_edge_plane32 (False: the exact float64 kernel; results are identical)
+EDGE_PLANE32 = True
 
 
 def disk_mask(center_rc, radius: float, shape) -> np.ndarray:

@@ -1,7 +1,8 @@
-// Timing attribution for gauss2d_mm (pylinac_amd/csrc/gaussian_mm.hip): the kernel source is compiled here with
-// -DPL_G2D_VARIANT=<bits> (see the switch list next to PL_G2D_VARIANT in that file) and timed on 256 x 1024 x 1024 uint16
-// frames, sigma 5.  Variants other than 0 compute garbage: this is a stopwatch, not a test.
-//   scripts/build_g2d_variants.sh 0 3 7 ...   ->  scripts/ubench/g2d_v<bits>
+// Sustained-loop timer of gauss2d_mm (pylinac_amd/csrc/gaussian_mm.hip), the product kernel's source compiled in here,
+// on 256 x 1024 x 1024 uint16 frames, sigma 5; with an idle time given, also the DVFS ramp after that much idleness.
+//   g2d_loop [frames=256] [data: 0 ramp+noise | 1 EPID-like | 2 low-toggle] [launches=10] [idle_ms]
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -mllvm -amdgpu-mfma-vgpr-form -Wno-unused-value \
+//         scripts/ubench/gauss2d_loop.hip -o scripts/ubench/g2d_loop
 #include "../../pylinac_amd/csrc/gaussian_mm.hip"
 
 #include <time.h>
@@ -69,27 +70,7 @@ int main(int argc, char** argv) {
     }
     printf("\n");
   }
-#if PL_G2D_TIMING
-  {
-    std::vector<unsigned long long> dbg(4096 * 8 * 4);
-    hipMemcpyFromSymbol(dbg.data(), HIP_SYMBOL(g2d_dbg), dbg.size() * 8);
-    const int wgs = n * 4 < 4096 ? n * 4 : 4096;
-    const char* names[4] = {"W+load-issue", "axis0", "barrier", "axis1"};
-    for (int wv = 0; wv < 8; ++wv) {
-      printf("  wave %d:", wv);
-      double tot = 0;
-      for (int k = 0; k < 4; ++k) {
-        double a = 0;
-        for (int b = 0; b < wgs; ++b) a += (double)dbg[(b * 8 + wv) * 4 + k];
-        a /= wgs * 64.0;                                       // per step (64 steps per workgroup at 1024 rows)
-        tot += a;
-        printf("  %s %7.0f", names[k], a);
-      }
-      printf("   = %7.0f memtime ticks per step\n", tot);
-    }
-  }
-#endif
-  printf("variant %3d: %.4f ms per launch of %d frames, %s data (%s)\n", PL_G2D_VARIANT, ms / iters, n, epid == 2 ? "low-toggle (1000 + 2 random bits)" : epid ? "EPID-like" : "ramp+noise",
+  printf("%.4f ms per launch of %d frames, %s data (%s)\n", ms / iters, n, epid == 2 ? "low-toggle (1000 + 2 random bits)" : epid ? "EPID-like" : "ramp+noise",
          hipGetErrorString(hipGetLastError()));
   return 0;
 }
