@@ -15,10 +15,13 @@ independent frames (weak scaling by default, `--scaling strong` splits the 256 f
 no data-path collective) and ends each step with the one all-gather of the per-image scalar records.
 Rank 0 prints ONE JSON line.
 
-At N = 1 the line also carries `configs`: BASELINE configs #3 (picket fence), #4 (Winston-Lutz) and #5
-(CatPhan CTP528) on their SURVEY 8d seeded generators, each with its own fraction of the HBM-read
-roofline and its own CPU baseline, and `cpu_baseline` (single thread + one worker per host core) for the
-headline workload.
+A plain run does only what that line's headline figure needs: it sets up, warms up, times the steps,
+writes --dump-outputs and prints the line (its `roofline` comes from the HIP events of the timed steps).
+`--full` at N = 1 adds, after the timed steps, `sustained` (the same step once clocks have settled),
+`parity_sample` (a sample of the step's outputs against the CPU oracle), `configs`: BASELINE configs
+#3 (picket fence), #4 (Winston-Lutz) and #5 (CatPhan CTP528) on their SURVEY 8d seeded generators, each
+with its own fraction of the HBM-read roofline and its own CPU baseline, and `cpu_baseline` (single
+thread + one worker per host core) for the headline workload.
 """
 from __future__ import annotations
 
@@ -50,13 +53,16 @@ def parse():
     ap.add_argument("--height", type=int, default=1024)
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed steps also measure the sustained rate, the parity sample against the oracle, "
+                         "the other configurations and the CPU baselines (the --no-* switches below drop single parts)")
     ap.add_argument("--cpu-frames", type=int, default=24,
                     help="bounded CPU-baseline sample (frames through the oracle on one core, per repeat: 3 warm-up + 5 timed)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip BASELINE configs #3-#5")
-    ap.add_argument("--no-parity", action="store_true", help="skip the headline parity sample against the oracle")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-configs", action="store_true", help="--full without BASELINE configs #3-#5")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the headline parity sample against the oracle")
     ap.add_argument("--sustained-steps", type=int, default=150,
-                    help="N = 1: steps of the extra steady-state measurement taken AFTER the contract's timed region (0 = off)")
+                    help="--full: steps of the extra steady-state measurement taken AFTER the contract's timed region (0 = off)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
                          f"at most {DUMP_MAX_BYTES >> 20} MB in all; the thresholded frames as a fixed seeded sample of whole "
@@ -589,26 +595,27 @@ def main():
         }
         if dumped is not None:
             line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-        if world == 1 and args.sustained_steps > 0:
-            # The contract's W + K steps last ~25 ms: inside the power governor's ramp (an MI355X reaches its 1400 W cap under
-            # gauss2d_mm; after an idle period the first launches run at boost clocks, the next ~10 are throttled hard, and the
-            # clock settles over the following ~30 ms: profiles/r03_dvfs_ramp.txt).  `value` above is what the contract measures;
-            # this object reports the same step after the governor has settled -- the rate of a production loop.
-            for _ in range(max(args.sustained_steps // 3, 1)):
-                step()
-            drain()
-            torch.cuda.synchronize()
-            ts = time.perf_counter()
-            for _ in range(args.sustained_steps):
-                step()
-            drain()
-            torch.cuda.synchronize()
-            sdt = (time.perf_counter() - ts) / args.sustained_steps
-            line["sustained"] = {"steps": args.sustained_steps, "settle_steps": max(args.sustained_steps // 3, 1),
-                                 "ms_per_step": round(sdt * 1e3, 4), "value": round(n / sdt, 1), "unit": "images/s",
-                                 "note": "same step, timed after the contract's region once clocks / power have settled; "
-                                         "not the contract value"}
-        if world == 1:
+        if world == 1 and args.full:
+            if args.sustained_steps > 0:
+                # The contract's W + K steps last ~25 ms: inside the power governor's ramp (an MI355X reaches its 1400 W cap
+                # under gauss2d_mm; after an idle period the first launches run at boost clocks, the next ~10 are throttled
+                # hard, and the clock settles over the following ~30 ms: profiles/r03_dvfs_ramp.txt).  `value` above is what
+                # the contract measures; this object reports the same step after the governor has settled -- the rate of a
+                # production loop.
+                for _ in range(max(args.sustained_steps // 3, 1)):
+                    step()
+                drain()
+                torch.cuda.synchronize()
+                ts = time.perf_counter()
+                for _ in range(args.sustained_steps):
+                    step()
+                drain()
+                torch.cuda.synchronize()
+                sdt = (time.perf_counter() - ts) / args.sustained_steps
+                line["sustained"] = {"steps": args.sustained_steps, "settle_steps": max(args.sustained_steps // 3, 1),
+                                     "ms_per_step": round(sdt * 1e3, 4), "value": round(n / sdt, 1), "unit": "images/s",
+                                     "note": "same step, timed after the contract's region once clocks / power have settled; "
+                                             "not the contract value"}
             # a sample of what the timed steps produced, against the CPU oracle (outside the timed region)
             if not args.no_parity:
                 line["parity_sample"] = parity_epid(pipe.run(frames), frames)

@@ -1,5 +1,6 @@
 """bench.py --dump-outputs: what the last timed step computed, written as float32 / float64 .npy files under the 64 MB cap,
-identical from run to run with the same arguments, and equal to the CPU oracle's sequence on the same seeded frames.
+identical from run to run with the same arguments, and equal to the CPU oracle's sequence on the same seeded frames; a
+plain run's line leaves everything beyond the headline to --full.
 The CPU tests drive bench.py's main() on the emulated device (tests/bench_dryrun.py); the GPU test runs bench.py itself."""
 import json
 import os
@@ -11,8 +12,8 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--frames", "3", "--height", "96", "--width", "128", "--steps", "2", "--warmup", "1",
-         "--no-cpu-baseline", "--no-configs", "--no-parity", "--sustained-steps", "0"]
+SIZE = ["--frames", "3", "--height", "96", "--width", "128", "--steps", "2", "--warmup", "1"]
+SMALL = [*SIZE, "--no-cpu-baseline", "--no-configs", "--no-parity", "--sustained-steps", "0"]
 
 
 def _run(script, args, out_dir, timeout):
@@ -58,6 +59,20 @@ def test_bench_dump_outputs_dry_run(tmp_path):
     assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k], equal_nan=True) for k in a)
     assert set(lines[0]["dumped_outputs"]["arrays"]) == set(a)
     _check_against_oracle(a, epid_open_field_frames(3, 96, 128, seed0=1000).numpy())
+
+
+def test_plain_run_leaves_extras_to_full(tmp_path):
+    """Without --full the line carries the headline and its roofline only: no sustained steps, parity sample, other
+    configurations or CPU baselines.  --full adds the parts it is not told to drop, and the dumped step is the same."""
+    plain = _run("tests/bench_dryrun.py", SIZE, tmp_path / "a", timeout=900)
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0 and "roofline" in plain
+    assert not {"sustained", "parity_sample", "configs", "cpu_baseline"} & plain.keys(), plain.keys()
+    full = _run("tests/bench_dryrun.py", [*SIZE, "--full", "--no-configs", "--no-cpu-baseline", "--sustained-steps", "2"],
+                tmp_path / "b", timeout=900)
+    assert full["sustained"]["steps"] == 2 and full["parity_sample"]["ok"] is True
+    assert "configs" not in full and "cpu_baseline" not in full
+    a, b = _load(tmp_path / "a"), _load(tmp_path / "b")
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k], equal_nan=True) for k in a)
 
 
 def test_dump_outputs_samples_large_outputs(tmp_path):

@@ -1902,15 +1902,15 @@ def test_ground_promotes_like_numpy(dev):
 def test_bench_line_contract(dev):
     """bench.py prints ONE JSON line with the driver's keys: metric / value / unit / n_gpus / steps / warmup / ms_per_step /
     higher_is_better / scaling / vs_baseline / dtype / data / config.workload, the roofline object of the dominant kernel
-    (bound, achieved, peak, unit, frac, traffic) and the cpu_baseline object (value, unit, cores, kind, sample).  A short run
-    on small frames (the default size is what the driver times)."""
+    (bound, achieved, peak, unit, frac, traffic) and, with --full, the cpu_baseline object (value, unit, cores, kind, sample).
+    A short run on small frames (the default size is what the benchmark times)."""
     import json
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames", "8", "--height", "256", "--width", "256",
-                        "--steps", "3", "--warmup", "1", "--no-configs", "--cpu-frames", "2"],
+                        "--steps", "3", "--warmup", "1", "--full", "--no-configs", "--cpu-frames", "2"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
