@@ -844,6 +844,38 @@ int pl_colparts_profile_fwxm(const uint32_t* d_parts, int64_t n, int bands, int 
                              int cap, double* d_profile, int32_t* d_count, int32_t* d_idx, int32_t* d_left_base,
                              int32_t* d_right_base, double* d_props, int32_t* d_status, double* d_fwxm, void* stream);
 
+/* ---- FieldAnalysis over a stack of frames (field_analysis.analyze_batch) ---------------------------------------------------
+ * pl_field_center_sums: np.sum(frame, 0) and np.sum(frame, 1) of every uint16 / int16 frame in one read of it, the sums
+ * FieldAnalysis._determine_center hands to SingleProfile (pylinac/field_analysis.py:488-506).  d_cols int64 [n][w] (zeroed here),
+ * d_rows float64 [n][h]; both exact.  w <= 4096. */
+int pl_field_center_sums(const void* in, int dtype, int64_t n, int h, int w, unsigned long long* d_cols, double* d_rows,
+                         void* stream);
+
+/* pl_field_strips: FieldAnalysis._get_horiz_values / _get_vert_values (pylinac/field_analysis.py:1068-1117) with a centre per
+ * frame: d_pos float64 [n][2] = (vert_position, horiz_position); the strip bounds are _strip_edges' arithmetic on the device
+ * (round half to even), written to d_edges int32 [n][4] = bottom, top, left, right; d_horiz float64 [n][w] =
+ * np.mean(frame[bottom:top, :], 0), d_vert float64 [n][h] = np.mean(frame[:, left:right], 1) in pl_reduce_axis' orders.
+ * uint16, int16, float64 frames. */
+int pl_field_strips(const void* in, int dtype, int64_t n, int h, int w, const double* d_pos, double vert_width,
+                    double horiz_width, double* d_horiz, double* d_vert, int32_t* d_edges, void* stream);
+
+/* pl_field_windows: SingleProfile.field_data (pylinac/core/profile.py:1463-1633) and the flatness / symmetry reductions over its
+ * "field values" (pylinac/field_analysis.py:37-231) for n processed profiles d_values float64 [n][s] sharing d_x_indices [s],
+ * hung on d_anchor [n] with full width d_span [n].  d_stats float64 [n][16] = field lo, field hi, field width, core lo, core hi,
+ * number of field values, max, min, point-difference symmetry, PDQ IEC symmetry, area symmetry, left slope, right slope,
+ * "top" window start, "top" window length, value at round(anchor); d_top float64 [n][tcap] = the "top" window's y values (the
+ * first tcap); d_scratch float64 [n][s] workspace. */
+int pl_field_windows(const double* d_x_indices, const double* d_values, int64_t n, int s, const double* d_anchor,
+                     const double* d_span, double in_field_ratio, double slope_exclusion_ratio, int tcap, double* d_stats,
+                     double* d_top, double* d_scratch, void* stream);
+
+/* pl_peak_ips_rows: SingleProfile.fwxm_data's left_ips / right_ips (pylinac/core/profile.py:1411-1461) at a per-profile height
+ * (SingleProfile.penumbra, INFLECTION_DERIVATIVE: profile.py:1791-1850): peaks as pl_find_peaks_regions returned them with
+ * max_number = 1; d_rel_height float64 [n][nq] = 1 - x / 100; d_out float64 [n][nq][2] (NaN without a peak). */
+int pl_peak_ips_rows(const double* d_x, int64_t n, int len, const int32_t* d_count, const int32_t* d_idx,
+                     const int32_t* d_left_base, const int32_t* d_right_base, const double* d_props, int cap,
+                     const double* d_rel_height, int nq, double* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,217 @@ __global__ void zoom_eval_kernel(const double* __restrict__ work, int L, int S, 
   out[i] = t;
 }
 
+
+// ------------------------------------------------------------- FieldAnalysis: SingleProfile.field_data windows
+// pl_field_windows: SingleProfile.field_data (pylinac/core/profile.py:1463-1633) and the protocol reductions over its "field
+// values" (pylinac/field_analysis.py:37-231) for every processed profile, one wave per profile:
+//   field = [anchor -/+ in_field_ratio * span / 2], core = [anchor -/+ slope_exclusion_ratio * field.width / 2]
+//   grid  = x_indices + (anchor - round(anchor)); first / last = the grid samples nearest the field's ends (first on a tie)
+//   field values f = y(grid[first .. last]), y = scipy's linear interp1d of the profile (extrapolating)
+//   max / min (Varian, Elekta flatness), 100 (f_k - f_{n-1-k}) / y(round(anchor)) at numpy's first argmax of |.|, the PDQ
+//   IEC ratio max(|l / r|, |r / l|) * sign at its first argmax, the Siemens area sums over f[: n // 2] and f[ceil(n / 2):]
+//   (numpy's pairwise summation, bit for bit), the two edge-slope regressions over _sample_points_in_physical_window
+//   (field.lo .. core.lo and core.hi .. field.hi), and the "top" window core.lo .. core.hi, whose samples go to d_top for the
+//   host's polyfit / L-BFGS-B.  float64 in the reference's operation order, no contraction (the build's -ffp-contract=off).
+constexpr int kFwStats = 16;
+
+__device__ __forceinline__ double fw_lookup(const double* __restrict__ xi, const double* __restrict__ v, int S, double q) {
+  int hi = lower_bound(xi, S, q);
+  hi = hi < 1 ? 1 : (hi > S - 1 ? S - 1 : hi);
+  const int lo = hi - 1;
+  const double slope = (v[hi] - v[lo]) / (xi[hi] - xi[lo]);
+  return slope * (q - xi[lo]) + v[lo];
+}
+
+// np.abs((xi + d) - p).argmin() over the whole wave: the smallest value, the lowest index among equal ones
+__device__ __forceinline__ int fw_nearest(const double* __restrict__ xi, int S, double d, double p) {
+  const int lane = threadIdx.x & 63;
+  double best = INFINITY;
+  int bi = S;
+  for (int j = lane; j < S; j += PL_WAVE) {
+    const double a = fabs((xi[j] + d) - p);
+    if (a < best) { best = a; bi = j; }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+  }
+  return bi < S ? bi : 0;
+}
+
+// np.searchsorted(xi, p, side) on the ascending x_indices: the number of samples < p ("left") or <= p ("right")
+__device__ __forceinline__ int fw_count(const double* __restrict__ xi, int S, double p, bool right) {
+  const int lane = threadIdx.x & 63;
+  int c = 0;
+  for (int j = lane; j < S; j += PL_WAVE) c += right ? (xi[j] <= p) : (xi[j] < p);
+  return pl_wave_reduce(c, [](int a, int b) { return a + b; });
+}
+
+// SingleProfile._sample_points_in_physical_window (profile.py:1237-1283) -> [start, stop) of x_indices
+__device__ __forceinline__ void fw_window(const double* __restrict__ xi, int S, double a, double b, int& start, int& stop) {
+  const double lo = a <= b ? a : b, hi = a <= b ? b : a;
+  start = fw_count(xi, S, lo, false);
+  stop = fw_count(xi, S, hi, true);
+  if (stop - start < 3) {
+    const int p = fw_nearest(xi, S, 0.0, lo), q = fw_nearest(xi, S, 0.0, hi);
+    start = min(p, q);
+    stop = max(p, q) + 1;
+  }
+  if (stop - start < 3) {
+    const int end = min(S, max(0, fw_nearest(xi, S, 0.0, (lo + hi) / 2.0) - 1) + 3);
+    start = max(0, end - 3);
+    stop = end;
+  }
+}
+
+// scipy.stats.linregress' slope over the window's samples (x_indices, y(x_indices))
+__device__ __forceinline__ double fw_slope(const double* __restrict__ xi, const double* __restrict__ v, int S, int start, int stop) {
+  const int lane = threadIdx.x & 63;
+  const int n = stop - start;
+  auto add = [](double a, double b) { return a + b; };
+  double sx = 0.0, sy = 0.0;
+  for (int j = start + lane; j < stop; j += PL_WAVE) { sx += xi[j]; sy += fw_lookup(xi, v, S, xi[j]); }
+  const double xm = pl_wave_reduce(sx, add) / n, ym = pl_wave_reduce(sy, add) / n;
+  double sxx = 0.0, sxy = 0.0;
+  for (int j = start + lane; j < stop; j += PL_WAVE) {
+    const double dx = xi[j] - xm, dy = fw_lookup(xi, v, S, xi[j]) - ym;
+    sxx += dx * dx;
+    sxy += dx * dy;
+  }
+  return (pl_wave_reduce(sxy, add) / n) / (pl_wave_reduce(sxx, add) / n);
+}
+
+// numpy's pairwise_sum (loops_utils.h: < 8 sequential from -0.0, <= 128 eight accumulators, else split at n / 2 rounded
+// down to a multiple of 8) without recursion: one lane walks the tree with a stack in LDS
+struct FwFrame { int start, n, stage; double left; };
+
+__device__ __forceinline__ double fw_leaf(const double* a, int n) {
+  if (n < 8) {
+    double res = -0.0;
+    for (int i = 0; i < n; ++i) res += a[i];
+    return res;
+  }
+  double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
+  int i = 8;
+  for (; i < n - (n % 8); i += 8) {
+    r0 += a[i]; r1 += a[i + 1]; r2 += a[i + 2]; r3 += a[i + 3];
+    r4 += a[i + 4]; r5 += a[i + 5]; r6 += a[i + 6]; r7 += a[i + 7];
+  }
+  double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+  for (; i < n; ++i) res += a[i];
+  return res;
+}
+
+__device__ __forceinline__ int fw_split(int n) { const int n2 = n / 2; return n2 - n2 % 8; }
+
+__device__ double fw_pairwise(const double* a, int n, FwFrame* st) {
+  if (n <= 128) return fw_leaf(a, n);
+  int top = 0;
+  st[top++] = FwFrame{0, n, 0, 0.0};
+  for (;;) {
+    FwFrame& f = st[top - 1];
+    if (f.n > 128) {
+      f.stage = 1;
+      st[top++] = FwFrame{f.start, fw_split(f.n), 0, 0.0};
+      continue;
+    }
+    double r = fw_leaf(a + f.start, f.n);
+    --top;
+    while (top > 0) {
+      FwFrame& p = st[top - 1];
+      if (p.stage == 1) {
+        p.left = r;
+        p.stage = 2;
+        const int n2 = fw_split(p.n);
+        st[top++] = FwFrame{p.start + n2, p.n - n2, 0, 0.0};
+        break;
+      }
+      r = p.left + r;
+      --top;
+    }
+    if (top == 0) return r;
+  }
+}
+
+__global__ void __launch_bounds__(PL_WAVE)
+field_windows_kernel(const double* __restrict__ xi, const double* __restrict__ values, int S,
+                     const double* __restrict__ anchor, const double* __restrict__ span, double in_field_ratio,
+                     double slope_exclusion_ratio, int tcap, double* __restrict__ stats, double* __restrict__ top_y,
+                     double* __restrict__ fv_scratch) {
+  __shared__ FwFrame stack[32];
+  const int64_t row = blockIdx.x;
+  const int lane = threadIdx.x;
+  const double* v = values + row * (int64_t)S;
+  double* o = stats + row * kFwStats;
+  double* fv = fv_scratch + row * (int64_t)S;
+  const double c = anchor[row], sp = span[row];
+  if (!(fabs(c) < 1e9) || !(fabs(sp) < 1e9)) {            // no edges: nothing to measure (NaN in, NaN out)
+    if (lane < kFwStats) o[lane] = (lane == 13 || lane == 14 || lane == 5) ? 0.0 : NAN;
+    return;
+  }
+  const double full = in_field_ratio * sp;
+  const double flo = c - full / 2.0, fhi = c + full / 2.0;
+  const double fwidth = fhi - flo;
+  const double core = slope_exclusion_ratio * fwidth;
+  const double clo = c - core / 2.0, chi = c + core / 2.0;
+  const double rc = rint(c), d = c - rc;
+  const int first = fw_nearest(xi, S, d, flo), last = fw_nearest(xi, S, d, fhi);
+  const int n = last - first + 1;
+  const double cax = fw_lookup(xi, v, S, rc);
+  double mx = -INFINITY, mn = INFINITY;
+  for (int k = lane; k < n; k += PL_WAVE) {
+    const double f = fw_lookup(xi, v, S, xi[first + k] + d);
+    fv[k] = f;
+    mx = f > mx ? f : mx;
+    mn = f < mn ? f : mn;
+  }
+  mx = pl_wave_reduce(mx, [](double a, double b) { return a > b ? a : b; });
+  mn = pl_wave_reduce(mn, [](double a, double b) { return a < b ? a : b; });
+  __syncthreads();
+  // point difference and PDQ IEC: first argmax of |.| (strict > per lane over ascending k, lowest k across lanes)
+  double pd = NAN, pd_abs = -1.0, pq = NAN, pq_abs = -1.0;
+  int pd_k = n, pq_k = n;
+  for (int k = lane; k < n; k += PL_WAVE) {
+    const double lt = fv[k], rt = fv[n - 1 - k];
+    const double s1 = (100.0 * (lt - rt)) / cax;
+    if (fabs(s1) > pd_abs) { pd_abs = fabs(s1); pd = s1; pd_k = k; }
+    const double q1 = lt / rt, q2 = rt / lt;
+    const double a1 = fabs(q1), a2 = fabs(q2);
+    const double sgn_src = a1 > a2 ? q1 : q2;
+    const double sgn = sgn_src > 0.0 ? 1.0 : (sgn_src < 0.0 ? -1.0 : (sgn_src == 0.0 ? 0.0 : sgn_src));
+    const double mxq = a2 > a1 ? a2 : a1;                    // python's max(a, b): b only if b > a
+    const double s2 = mxq * sgn;
+    if (fabs(s2) > pq_abs) { pq_abs = fabs(s2); pq = s2; pq_k = k; }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const double oa = __shfl_xor(pd_abs, off, 64), ov = __shfl_xor(pd, off, 64);
+    const int ok = __shfl_xor(pd_k, off, 64);
+    if (oa > pd_abs || (oa == pd_abs && ok < pd_k)) { pd_abs = oa; pd = ov; pd_k = ok; }
+    const double qa = __shfl_xor(pq_abs, off, 64), qv = __shfl_xor(pq, off, 64);
+    const int qk = __shfl_xor(pq_k, off, 64);
+    if (qa > pq_abs || (qa == pq_abs && qk < pq_k)) { pq_abs = qa; pq = qv; pq_k = qk; }
+  }
+  int ls, le, rs, re, ts, te;
+  fw_window(xi, S, flo, clo, ls, le);
+  fw_window(xi, S, chi, fhi, rs, re);
+  fw_window(xi, S, clo, chi, ts, te);
+  const double slope_l = fw_slope(xi, v, S, ls, le), slope_r = fw_slope(xi, v, S, rs, re);
+  const int tn = te - ts;
+  for (int j = lane; j < tn && j < tcap; j += PL_WAVE) top_y[row * (int64_t)tcap + j] = fw_lookup(xi, v, S, xi[ts + j]);
+  if (lane == 0) {
+    double area = NAN;
+    if (n > 0) {
+      const int half_lo = n / 2, half_hi = (n + 1) / 2;
+      const double al = fw_pairwise(fv, half_lo, stack), ar = fw_pairwise(fv + half_hi, n - half_hi, stack);
+      area = (100.0 * (al - ar)) / (al + ar);
+    }
+    o[0] = flo; o[1] = fhi; o[2] = fwidth; o[3] = clo; o[4] = chi; o[5] = (double)n;
+    o[6] = n > 0 ? mx : NAN; o[7] = n > 0 ? mn : NAN; o[8] = pd; o[9] = pq; o[10] = area;
+    o[11] = slope_l; o[12] = slope_r; o[13] = (double)ts; o[14] = (double)tn; o[15] = cax;
+  }
+}
+
 }  // namespace
 
 extern "C" int pl_zoom1d_cubic(const double* y, int64_t n_profiles, int length, int out_length, int grid_mode,
@@ -243,4 +454,17 @@ extern "C" int pl_interp1d(const double* x, int64_t x_stride, const double* y, i
                        x_stride, y, M, length, xq, n_query, total, out);
   }
   return pl_check_launch("pl_interp1d");
+}
+
+extern "C" int pl_field_windows(const double* d_x_indices, const double* d_values, int64_t n, int s, const double* d_anchor,
+                                const double* d_span, double in_field_ratio, double slope_exclusion_ratio, int tcap,
+                                double* d_stats, double* d_top, double* d_scratch, void* stream) {
+  PL_REQUIRE(d_x_indices && d_values && d_anchor && d_span && d_stats && d_top && d_scratch, "null pointer");
+  PL_REQUIRE(n >= 0 && s >= 2 && tcap >= 1, "bad shape");
+  PL_REQUIRE(s <= (1 << 21), "profile too long");
+  if (n == 0) return PL_OK;
+  PL_REQUIRE(n <= 0x7fffffffLL, "batch too large");
+  hipLaunchKernelGGL(field_windows_kernel, dim3((unsigned)n), dim3(PL_WAVE), 0, (hipStream_t)stream, d_x_indices, d_values, s,
+                     d_anchor, d_span, in_field_ratio, slope_exclusion_ratio, tcap, d_stats, d_top, d_scratch);
+  return pl_check_launch("pl_field_windows");
 }

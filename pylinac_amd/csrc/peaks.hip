@@ -163,6 +163,34 @@ peak_valley_kernel(const double* __restrict__ x, int64_t nprof, int64_t stride, 
   }
 }
 
+
+// pl_peak_ips_rows: the FWXM edges of SingleProfile.fwxm_data (pylinac/core/profile.py:1411-1461) at a DIFFERENT height per
+// profile, as SingleProfile.penumbra's INFLECTION_DERIVATIVE branch asks for (profile.py:1791-1850: fwxm_data(x) with x from
+// the inflection values): scipy's peak_widths of the one peak a max_number = 1 search kept (its index, bases and prominence do
+// not depend on the height) at rel_height[i][q] -> left_ips / right_ips.  One wave per profile; NaN where it has no peak.
+__global__ void __launch_bounds__(PL_WAVE)
+peak_ips_rows_kernel(const double* __restrict__ x, int len, const int32_t* __restrict__ count, const int32_t* __restrict__ idx,
+                     const int32_t* __restrict__ lb, const int32_t* __restrict__ rb, const double* __restrict__ props, int cap,
+                     const double* __restrict__ rel, int nq, double* __restrict__ out) {
+  const int64_t row = blockIdx.x;
+  const double* xs = x + row * (int64_t)len;
+  for (int q = 0; q < nq; ++q) {
+    double lip = NAN, rip = NAN;
+    const double r = rel[row * nq + q];
+    if (count[row] > 0 && r == r) {
+      const int pk = idx[row * cap], l = lb[row * cap], rr = rb[row * cap];
+      const double prom = props[(row * 6 + 1) * cap];
+      const Widths w = peak_width(xs, pk, l, rr, prom, r);
+      lip = w.lip;
+      rip = w.rip;
+    }
+    if (threadIdx.x == 0) {
+      out[(row * nq + q) * 2] = lip;
+      out[(row * nq + q) * 2 + 1] = rip;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int pl_fwxm_record(const int32_t* d_count, const int32_t* d_idx, const double* d_props,
@@ -322,4 +350,16 @@ extern "C" int pl_peak_valley_regions(const double* d_x, int64_t n, int len, int
                      lds * (kThreads / PL_WAVE), (hipStream_t)stream, d_x, n, stride, len, R, (int)lds, maxc, cap_p, cap_v,
                      d_pk_count, d_pk_height, d_vl_count, d_vl_value, d_means);
   return pl_check_launch("pl_peak_valley_regions");
+}
+
+extern "C" int pl_peak_ips_rows(const double* d_x, int64_t n, int len, const int32_t* d_count, const int32_t* d_idx,
+                                const int32_t* d_left_base, const int32_t* d_right_base, const double* d_props, int cap,
+                                const double* d_rel_height, int nq, double* d_out, void* stream) {
+  PL_REQUIRE(d_x && d_count && d_idx && d_left_base && d_right_base && d_props && d_rel_height && d_out, "null pointer");
+  PL_REQUIRE(n >= 0 && len >= 1 && cap >= 1 && nq >= 1, "bad shape");
+  if (n == 0) return PL_OK;
+  PL_REQUIRE(n <= 0x7fffffffLL, "batch too large");
+  hipLaunchKernelGGL(peak_ips_rows_kernel, dim3((unsigned)n), dim3(PL_WAVE), 0, (hipStream_t)stream, d_x, len, d_count, d_idx,
+                     d_left_base, d_right_base, d_props, cap, d_rel_height, nq, d_out);
+  return pl_check_launch("pl_peak_ips_rows");
 }

@@ -208,6 +208,100 @@ __global__ void colsum_to_mean_kernel(const unsigned long long* __restrict__ cs,
   if (i < total) out[i] = (double)cs[i] / (double)h;  // np.mean of integers: float64 sum / count
 }
 
+
+// ------------------------------------------------------------- FieldAnalysis: centre sums and strips
+// pl_field_center_sums: np.sum(frame, 0) and np.sum(frame, 1) of a 16-bit frame in one read.  A workgroup takes a band of
+// kCsBand rows; wave w sums rows w, w + 4, ... of the band.  A row's sum is the wave's (int64, exact); a column's partial sum
+// over the wave's rows stays in the wave's own LDS slice (int32: at most 64 rows of |v| <= 65535 per wave and band, lane-owned
+// columns, no atomics), the four slices are added and one int64 atomic per column and band goes to d_cols.
+constexpr int kCsBand = 256;
+constexpr int kCsWaves = kThreads / PL_WAVE;
+
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+field_center_sums_kernel(const T* __restrict__ in, int h, int w, int bands, unsigned long long* __restrict__ cols,
+                         double* __restrict__ rows) {
+  extern __shared__ int cs_lds[];                       // [kCsWaves][w]
+  const int band = blockIdx.x % bands;
+  const size_t frame = blockIdx.x / bands;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  int* mine = cs_lds + (size_t)wave * w;
+  for (int c = lane; c < w; c += PL_WAVE) mine[c] = 0;
+  const int r0 = band * kCsBand, r1 = min(r0 + kCsBand, h);
+  const T* f = in + frame * (size_t)h * w;
+  for (int r = r0 + wave; r < r1; r += kCsWaves) {
+    const T* p = f + (size_t)r * w;
+    long long acc = 0;
+    for (int c = lane; c < w; c += PL_WAVE) {
+      const int v = (int)p[c];
+      acc += v;
+      mine[c] += v;
+    }
+    acc = pl_wave_reduce(acc, [](long long a, long long b) { return a + b; });
+    if (lane == 0) rows[frame * h + r] = (double)acc;
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < w; c += kThreads) {
+    long long s = 0;
+    for (int k = 0; k < kCsWaves; ++k) s += cs_lds[(size_t)k * w + c];
+    atomicAdd(cols + frame * w + c, (unsigned long long)s);
+  }
+}
+
+// _strip_edges (FieldAnalysis._get_horiz_values / _get_vert_values): lo = max(int(round(L * pos - L * width / 2)), 0),
+// hi = min(int(round(L * pos + L * width / 2) + 1), L); python's round is half-to-even = rint.  A non-finite position
+// (the centre search found no field) gives the empty strip [0, 0).
+__device__ __forceinline__ void strip_edges(int length, double pos, double width, int& lo, int& hi) {
+  const double a = (double)length * pos, b = (double)length * width / 2.0;
+  const double l = rint(a - b), u = rint(a + b);
+  if (!(l == l) || !(u == u) || fabs(l) > 1e9 || fabs(u) > 1e9) { lo = 0; hi = 0; return; }
+  lo = max((int)l, 0);
+  hi = min((int)u + 1, length);
+  if (hi < lo) hi = lo;                                   // an empty slice, as python's a[lo:hi]
+}
+
+// pl_field_strips: per frame f with centre ratios pos[f] = (vert_ratio, horiz_ratio)
+//   horiz[f] = np.mean(frame[bottom:top, :], 0)   [w]   (rows from horiz_ratio * h)
+//   vert[f]  = np.mean(frame[:, left:right], 1)   [h]   (columns from vert_ratio * w)
+// Blocks 0 .. col_tiles - 1 of a frame: one column per lane, rows summed in order (reduce_axis0_kernel's order); the
+// remaining blocks: one row per wave, the strip's columns lane-strided and wave-reduced (reduce_axis1_kernel's order on
+// the sliced copy).  Only the strip's rows and columns are read.  Block 0 writes edges[f] = bottom, top, left, right.
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+field_strips_kernel(const T* __restrict__ in, int h, int w, const double* __restrict__ pos, double vwidth, double hwidth,
+                    int col_tiles, int row_groups, double* __restrict__ horiz, double* __restrict__ vert,
+                    int32_t* __restrict__ edges) {
+  using A = typename Acc<T>::type;
+  const int per_frame = col_tiles + row_groups;
+  const size_t frame = blockIdx.x / per_frame;
+  const int part = blockIdx.x % per_frame;
+  const T* f = in + frame * (size_t)h * w;
+  int bottom, top, left, right;
+  strip_edges(h, pos[2 * frame + 1], hwidth, bottom, top);
+  strip_edges(w, pos[2 * frame], vwidth, left, right);
+  if (part == 0 && threadIdx.x == 0) {
+    int32_t* e = edges + frame * 4;
+    e[0] = bottom; e[1] = top; e[2] = left; e[3] = right;
+  }
+  if (part < col_tiles) {
+    const int c = part * kThreads + threadIdx.x;
+    if (c >= w) return;
+    A acc = 0;
+    for (int r = bottom; r < top; ++r) acc += (A)f[(size_t)r * w + c];
+    horiz[frame * w + c] = finish<T>(acc, PL_MEAN, top - bottom);
+  } else {
+    const int r = (part - col_tiles) * (kThreads / PL_WAVE) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= h) return;
+    const T* p = f + (size_t)r * w + left;
+    const int n = right - left;
+    A acc = 0;
+    for (int c = lane; c < n; c += PL_WAVE) acc += (A)p[c];
+    acc = pl_wave_reduce(acc, [](A a, A b) { return a + b; });
+    if (lane == 0) vert[frame * h + r] = finish<T>(acc, PL_MEAN, n);
+  }
+}
+
 }  // namespace
 
 extern "C" int pl_colsum_to_mean(const unsigned long long* d_colsum, int64_t n, int w, int h,
@@ -296,4 +390,40 @@ extern "C" int pl_median3_threshold_colparts_u16(const uint16_t* in, uint16_t* o
   hipLaunchKernelGGL(median3_threshold_colsum_kernel<true>, dim3((unsigned)(n * bands * col_groups)), dim3(kMtWaves * PL_WAVE), 0,
                      (hipStream_t)stream, in, out, h, w, bands, col_groups, d_thr, (unsigned long long*)nullptr, d_parts);
   return pl_check_launch("pl_median3_threshold_colparts_u16");
+}
+
+extern "C" int pl_field_center_sums(const void* in, int dtype, int64_t n, int h, int w, unsigned long long* d_cols,
+                                    double* d_rows, void* stream) {
+  PL_REQUIRE(in && d_cols && d_rows, "null pointer");
+  PL_REQUIRE(n >= 0 && h > 0 && w > 0, "bad shape");
+  PL_REQUIRE(dtype == PL_U16 || dtype == PL_I16, "pl_field_center_sums takes uint16 / int16 frames");
+  PL_REQUIRE((int64_t)w * kCsWaves * 4 <= 65536, "frame wider than 4096 columns");
+  if (n == 0) return PL_OK;
+  const int bands = (int)pl_cdiv(h, kCsBand);
+  PL_REQUIRE(n * bands <= 0x7fffffffLL, "batch too large");
+  hipStream_t st = (hipStream_t)stream;
+  PL_REQUIRE(hipMemsetAsync(d_cols, 0, (size_t)n * w * sizeof(unsigned long long), st) == hipSuccess, "memset failed");
+  const size_t lds = (size_t)w * kCsWaves * sizeof(int);
+  if (dtype == PL_U16)
+    hipLaunchKernelGGL(field_center_sums_kernel<unsigned short>, dim3((unsigned)(n * bands)), dim3(kThreads), lds, st,
+                       (const unsigned short*)in, h, w, bands, d_cols, d_rows);
+  else
+    hipLaunchKernelGGL(field_center_sums_kernel<short>, dim3((unsigned)(n * bands)), dim3(kThreads), lds, st,
+                       (const short*)in, h, w, bands, d_cols, d_rows);
+  return pl_check_launch("pl_field_center_sums");
+}
+
+extern "C" int pl_field_strips(const void* in, int dtype, int64_t n, int h, int w, const double* d_pos, double vert_width,
+                               double horiz_width, double* d_horiz, double* d_vert, int32_t* d_edges, void* stream) {
+  PL_REQUIRE(in && d_pos && d_horiz && d_vert && d_edges, "null pointer");
+  PL_REQUIRE(n >= 0 && h > 0 && w > 0, "bad shape");
+  PL_REQUIRE(dtype == PL_U16 || dtype == PL_I16 || dtype == PL_F64, "pl_field_strips takes uint16 / int16 / float64 frames");
+  if (n == 0) return PL_OK;
+  const int col_tiles = (int)pl_cdiv(w, kThreads), row_groups = (int)pl_cdiv(h, kThreads / PL_WAVE);
+  PL_REQUIRE(n * (col_tiles + row_groups) <= 0x7fffffffLL, "batch too large");
+  PL_DISPATCH_DTYPE(dtype, T,
+                    hipLaunchKernelGGL(field_strips_kernel<T>, dim3((unsigned)(n * (col_tiles + row_groups))), dim3(kThreads),
+                                       0, (hipStream_t)stream, (const T*)in, h, w, d_pos, vert_width, horiz_width, col_tiles,
+                                       row_groups, d_horiz, d_vert, d_edges));
+  return pl_check_launch("pl_field_strips");
 }

@@ -440,6 +440,69 @@ def reduce_axis(frames: torch.Tensor, axis: int, op: str = "mean") -> torch.Tens
     return out
 
 
+
+def field_center_sums(frames: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``np.sum(frame, 0)`` and ``np.sum(frame, 1)`` per frame -> float64 ([N, W], [N, H]) (FieldAnalysis._determine_center).
+    16-bit frames: one read of each frame (``pl_field_center_sums``, exact int64 sums); float64 frames: the two
+    ``pl_reduce_axis`` passes (axis 0 bitwise numpy's, axis 1 within its pairwise rounding)."""
+    x = _frames(frames)
+    n, h, w = x.shape
+    if x.dtype == torch.float64:
+        return reduce_axis(x, 0, "sum"), reduce_axis(x, 1, "sum")
+    if x.dtype not in (torch.uint16, torch.int16):
+        raise TypeError("field_center_sums takes uint16, int16 or float64 frames")
+    cols = torch.empty((n, w), dtype=torch.int64, device=x.device)
+    rows = torch.empty((n, h), dtype=torch.float64, device=x.device)
+    check(_lib.load().pl_field_center_sums(x.data_ptr(), _dt(x), n, h, w, cols.data_ptr(), rows.data_ptr(), _stream()),
+          "pl_field_center_sums")
+    return cols.to(torch.float64), rows
+
+
+def field_strips(frames: torch.Tensor, pos: torch.Tensor, vert_width: float, horiz_width: float):
+    """FieldAnalysis' two strip profiles with a centre per frame: ``pos`` float64 [N, 2] = (vert_position, horiz_position)
+    -> (horiz float64 [N, W], vert float64 [N, H], edges int32 [N, 4] = bottom, top, left, right)."""
+    x = _frames(frames)
+    n, h, w = x.shape
+    if x.dtype not in (torch.uint16, torch.int16, torch.float64):
+        raise TypeError("field_strips takes uint16, int16 or float64 frames")
+    p = pos.to(device=x.device, dtype=torch.float64).contiguous()
+    if tuple(p.shape) != (n, 2):
+        raise ValueError("pos must be [N, 2]")
+    horiz = torch.empty((n, w), dtype=torch.float64, device=x.device)
+    vert = torch.empty((n, h), dtype=torch.float64, device=x.device)
+    edges = torch.empty((n, 4), dtype=torch.int32, device=x.device)
+    check(_lib.load().pl_field_strips(x.data_ptr(), _dt(x), n, h, w, p.data_ptr(), float(vert_width), float(horiz_width),
+                                      horiz.data_ptr(), vert.data_ptr(), edges.data_ptr(), _stream()), "pl_field_strips")
+    return horiz, vert, edges
+
+
+FIELD_WINDOW_STATS = ("field_lo", "field_hi", "field_width", "core_lo", "core_hi", "n_field", "max", "min",
+                      "symmetry_point_difference", "symmetry_pdq_iec", "symmetry_area", "left_slope", "right_slope",
+                      "top_start", "top_len", "cax_value")
+
+
+def field_windows(x_indices: torch.Tensor, values: torch.Tensor, anchor: torch.Tensor, span: torch.Tensor,
+                  in_field_ratio: float, slope_exclusion_ratio: float, tcap: int):
+    """``SingleProfile.field_data`` windows and the protocol reductions per processed profile (``pl_field_windows``):
+    values float64 [N, S] sharing x_indices [S], anchor / span float64 [N] -> (stats float64 [N, 16] in FIELD_WINDOW_STATS
+    order, top float64 [N, tcap] = the "top" window's first tcap y values)."""
+    v = values.to(torch.float64).contiguous()
+    xi = x_indices.to(device=v.device, dtype=torch.float64).contiguous()
+    n, s = v.shape
+    if xi.numel() != s:
+        raise ValueError("x_indices and values must have the same length")
+    a = anchor.to(device=v.device, dtype=torch.float64).reshape(-1).contiguous()
+    sp = span.to(device=v.device, dtype=torch.float64).reshape(-1).contiguous()
+    if a.numel() != n or sp.numel() != n:
+        raise ValueError("anchor and span must be [N]")
+    stats = torch.empty((n, len(FIELD_WINDOW_STATS)), dtype=torch.float64, device=v.device)
+    top = torch.zeros((n, int(tcap)), dtype=torch.float64, device=v.device)
+    scratch = torch.empty((n, s), dtype=torch.float64, device=v.device)
+    check(_lib.load().pl_field_windows(xi.data_ptr(), v.data_ptr(), n, s, a.data_ptr(), sp.data_ptr(), float(in_field_ratio),
+                                       float(slope_exclusion_ratio), int(tcap), stats.data_ptr(), top.data_ptr(),
+                                       scratch.data_ptr(), _stream()), "pl_field_windows")
+    return stats, top
+
 def threshold_colsum_u16(frames: torch.Tensor, thr_i32: torch.Tensor, out=None, colsum=None):
     x = _frames(frames)
     if x.dtype != torch.uint16:
@@ -557,6 +620,20 @@ def find_peaks_batch(profiles: torch.Tensor, cap: int | None = None, lens: torch
     )
     return res
 
+
+
+def peak_ips_rows(profiles: torch.Tensor, peaks: "PeakBatch", rel_height: torch.Tensor) -> torch.Tensor:
+    """left_ips / right_ips of the one peak of a ``max_number=1`` search at a per-profile ``rel_height`` float64 [N, Q]
+    (``1 - fwxm_height``) -> float64 [N, Q, 2] (NaN where the profile has no peak)."""
+    x = profiles.to(torch.float64).contiguous()
+    n, length = x.shape
+    r = rel_height.to(device=x.device, dtype=torch.float64).reshape(n, -1).contiguous()
+    out = torch.empty((n, r.shape[1], 2), dtype=torch.float64, device=x.device)
+    check(_lib.load().pl_peak_ips_rows(x.data_ptr(), n, length, peaks.count.data_ptr(), peaks.idx.data_ptr(),
+                                       peaks.left_bases.data_ptr(), peaks.right_bases.data_ptr(), peaks.props.data_ptr(),
+                                       peaks.idx.shape[1], r.data_ptr(), r.shape[1], out.data_ptr(), _stream()),
+          "pl_peak_ips_rows")
+    return out
 
 def peak_valley_regions(profiles: torch.Tensor, peak_kwargs: list, valley_kwargs: list):
     """``find_peaks`` and, between the outermost peaks found, ``find_valleys`` for every (profile, region) pair in one launch

@@ -1202,6 +1202,15 @@ class SingleProfile(ProfileMixin):
             return fv.min()
 
 
+def _batch_geometric_center(values: torch.Tensor, x_indices: np.ndarray) -> dict:
+    """``SingleProfile.geometric_center`` (profile.py:1373-1385) for every row: the index is the middle sample mapped to
+    original coordinates (the same for every row of equal length), the value ``array_utils.geometric_center_value``."""
+    n, s = values.shape
+    idx = float(np.interp((s - 1) / 2.0, np.arange(s), np.asarray(x_indices, dtype=np.float64)))
+    val = (values[:, s // 2] + values[:, s // 2 - 1]) / 2.0 if s % 2 == 0 else values[:, (s - 1) // 2]
+    return {"index (exact)": torch.full((n,), idx, dtype=torch.float64, device=values.device), "value (exact)": val}
+
+
 @dataclass
 class HillEdgesBatch:
     """What ``SingleProfile(..., edge_detection_method=INFLECTION_HILL)`` holds and ``inflection_data()`` returns, for every
@@ -1280,6 +1289,9 @@ class HillEdgesBatch:
                 data[f"{side} gradient (exact) %/mm"] = rec[:, s, 5] * self.dpmm * 100
                 data[f"{side} penumbra width (exact) mm"] = rec[:, s, 4] / self.dpmm
         return data
+
+    def geometric_center(self) -> dict:
+        return _batch_geometric_center(self.values, self.x_indices)
 
 
 def _lib_error(msg: str):
@@ -1471,6 +1483,10 @@ class FWXMEdgesBatch:
         return {"index (rounded)": d["center index (rounded)"], "index (exact)": d["center index (exact)"],
                 "value (@rounded)": d["center value (@rounded)"]}
 
+    def geometric_center(self) -> dict:
+        """``SingleProfile.geometric_center`` (profile.py:1373-1385) for every row."""
+        return _batch_geometric_center(self.values, self.x_indices)
+
 
 def single_profile_fwhm_batch(values, dpmm: float | None = None, interpolation=Interpolation.LINEAR, ground: bool = True,
                               interpolation_resolution_mm: float = 0.1, interpolation_factor: float = 10,
@@ -1512,6 +1528,41 @@ class InflectionEdgesBatch:
             "right value (@rounded)": at(torch.round(right)),
             "right value (@exact)": at(right),
         }
+
+    def geometric_center(self) -> dict:
+        """``SingleProfile.geometric_center`` (profile.py:1373-1385) for every row."""
+        return _batch_geometric_center(self.values, self.x_indices)
+
+    def penumbra(self, lower: int = 20, upper: int = 80) -> dict:
+        """``SingleProfile.penumbra`` for the INFLECTION_DERIVATIVE method (profile.py:1791-1850) for every row: the FWXM edges
+        at heights scaled by each row's inflection values, ``max(v / max * lower / 50 * 100, 1)`` and
+        ``min(v / max * upper / 50 * 100, 99)``, from one peak search and one ``pl_peak_ips_rows`` launch ("left values" /
+        "right values", ragged, are left out).  Rows without edges hold NaN."""
+        if lower > upper:
+            raise ValueError("Upper penumbra value must be larger than the lower penumbra value")
+        infl = self.inflection_data()
+        vmax = self.values.amax(dim=1)
+        lv, rv = infl["left value (@exact)"], infl["right value (@exact)"]
+        one, ninety_nine = torch.ones_like(vmax), torch.full_like(vmax, 99.0)
+        x = torch.stack([torch.maximum(lv / vmax * lower / 50 * 100, one), torch.minimum(lv / vmax * upper / 50 * 100, ninety_nine),
+                         torch.maximum(rv / vmax * lower / 50 * 100, one), torch.minimum(rv / vmax * upper / 50 * 100, ninety_nine)],
+                        dim=1)
+        bad = torch.isnan(x) | (x < 0) | (x > 100)
+        rel = torch.where(bad, torch.full_like(x, float("nan")), 1 - x / 100)
+        pk = ops.find_peaks_batch(self.values, cap=1, fwxm_height=0.5, max_number=1)
+        ips = ops.peak_ips_rows(self.values, pk, rel)                                   # [N, 4, 2]
+        xi = torch.from_numpy(np.ascontiguousarray(self.x_indices)).to(self.values.device)
+        q = torch.stack([ips[:, 0, 0], ips[:, 1, 0], ips[:, 2, 1], ips[:, 3, 1]], dim=1)  # lower left, upper left, lower / upper right
+        orig = ops.index_to_original(xi, torch.nan_to_num(q).contiguous())
+        orig = torch.where(torch.isnan(q), q, orig)
+        data = {f"left {lower}% index (exact)": orig[:, 0], f"left {upper}% index (exact)": orig[:, 1],
+                f"right {lower}% index (exact)": orig[:, 2], f"right {upper}% index (exact)": orig[:, 3],
+                "left penumbra width (exact)": torch.abs(orig[:, 1] - orig[:, 0]),
+                "right penumbra width (exact)": torch.abs(orig[:, 3] - orig[:, 2])}
+        if self.dpmm:
+            data["left penumbra width (exact) mm"] = data["left penumbra width (exact)"] / self.dpmm
+            data["right penumbra width (exact) mm"] = data["right penumbra width (exact)"] / self.dpmm
+        return data
 
 
 def _inflection_edges_stage(vals: torch.Tensor, xi_dev: torch.Tensor, edge_smoothing_ratio: float, peak_cap: int):
