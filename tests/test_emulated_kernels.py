@@ -290,8 +290,10 @@ def test_emu_median_consumed_on_the_fly(emu):
 def test_emu_full_range_otsu_counter_overflow(emu):
     """otsu16_full_kernel (the fallback of pl_otsu16 / pl_median3_otsu16 for frames wider than the 38 912-bin window): 65 536
     packed 16-bit counters whose guard bit folds 32 768 counts away at a time.  Frames of > 32 768 pixels with one value
-    holding most of them, scattered (every add is a lane's own: the guard is crossed by single adds) and as flat areas (the
-    wave-uniform bulk add crosses it), twice over (two folds of one key), next to full-range noise; plain and median paths."""
+    holding most of them, scattered (every add is a lane's own: the guard is crossed by single adds), twice over (two folds of
+    one key), and a half shared by two heavy values at random (no wave row of it is flat after the median, so these are single
+    adds too: the wave-uniform bulk adds are the subject of tests/test_otsu_capacity.py), next to full-range noise; plain
+    and median paths."""
     from scipy import ndimage
 
     rng = np.random.default_rng(9)
@@ -301,8 +303,8 @@ def test_emu_full_range_otsu_counter_overflow(emu):
         noise = rng.integers(0, 65536, (3, h, w))
         a = noise.copy()
         a[0][rng.random((h, w)) < 0.75] = 777                           # scattered: ~74 000 single adds to one bin (two folds)
-        a[1][:, : w // 2] = 40000                                       # flat half: wave-uniform bulk adds
-        a[1][rng.random((h, w)) < 0.3] = 40001                          # ... broken up by a second heavy value
+        a[1][:, : w // 2] = 40000                                       # a heavy half ...
+        a[1][rng.random((h, w)) < 0.3] = 40001                          # ... broken up by a second heavy value: no flat wave row
         a[2] = np.where(rng.random((h, w)) < 0.5, 12, 65535)            # two values only, at the ends of the range
         a = (a - off).astype(dt)
         n = a.shape[0]

@@ -1016,9 +1016,10 @@ def test_median_consumed_on_the_fly_vs_scipy_and_oracle(dev):
 def test_full_range_otsu_counter_overflow_1024(dev):
     """The full-range Otsu kernel (65 536 packed 16-bit counters, guard bit, 32 768-count folds) under REAL concurrency: 1024 x
     1024 frames whose histogram has bins far beyond 32 767 -- one value on 75 % of the pixels scattered among full-range noise
-    (single adds cross the guard ~24 times for one key while 1 024 threads race), flat halves (wave-uniform bulk adds), two
-    values at the ends of the range, an EPID frame stretched to the full range -- against the oracle's Otsu on scipy's median;
-    plain frames (pl_otsu16) too.  uint16 and int16."""
+    (single adds cross the guard ~24 times for one key while 1 024 threads race), a half held by two heavy values at random
+    (40001 on 30 % of the pixels breaks every wave row of the 40000 half: single adds again -- the wave-uniform bulk adds
+    are the subject of tests/test_otsu_capacity.py), two values at the ends of the range, an EPID frame stretched to the
+    full range -- against the oracle's Otsu on scipy's median; plain frames (pl_otsu16) too.  uint16 and int16."""
     from scipy import ndimage
 
     from pylinac_amd import ops
