@@ -844,6 +844,22 @@ int pl_colparts_profile_fwxm(const uint32_t* d_parts, int64_t n, int bands, int 
                              int cap, double* d_profile, int32_t* d_count, int32_t* d_idx, int32_t* d_left_base,
                              int32_t* d_right_base, double* d_props, int32_t* d_status, double* d_fwxm, void* stream);
 
+/* The EPID step from the Gaussian plane on in ONE launch: pl_median3_threshold_colsum_u16's pass (`out` = the thresholded 3x3
+ * medians of `in`), and behind it, per frame, by the workgroup that finishes the frame last while the others threshold later
+ * frames: d_profile[n][w] = np.mean(out, 0), pl_find_peaks on it with `params` (outputs as pl_find_peaks), pl_fwxm_record's
+ * row d_fwxm[n][8], and d_record[n][9] = (double)d_thr[i], d_fwxm[i][0..7] -- the per-image record pipeline.EpidResult.record()
+ * returns.  Results are those of pl_median3_threshold_colsum_u16 -> pl_colsum_to_mean -> pl_find_peaks -> pl_fwxm_record, bit
+ * for bit.  d_ws: uint64 [n][w + 1] (column sums + arrival ticket of each frame), ALL ZERO on entry and all zero again when the
+ * launch has run: zero it once, when it is allocated, and give it to one launch at a time.  Frames as
+ * pl_median3_threshold_colsum_u16 (h > 1, w % 8 == 0, 16-byte aligned planes) and a search region whose tables fit 48 KiB of
+ * LDS (up to ~3 000 samples): pl_median3_threshold_profile_fwxm_covers(h, w, params) == 1; PL_ERR_INVALID_ARG otherwise. */
+int pl_median3_threshold_profile_fwxm_u16(const uint16_t* in, uint16_t* out, int64_t n, int h, int w, const int32_t* d_thr,
+                                          const pl_peak_params* params, int cap, double* d_profile, int32_t* d_count,
+                                          int32_t* d_idx, int32_t* d_left_base, int32_t* d_right_base, double* d_props,
+                                          int32_t* d_status, double* d_fwxm, double* d_record, unsigned long long* d_ws,
+                                          void* stream);
+int pl_median3_threshold_profile_fwxm_covers(int h, int w, const pl_peak_params* params);
+
 /* ---- FieldAnalysis over a stack of frames (field_analysis.analyze_batch) ---------------------------------------------------
  * pl_field_center_sums: np.sum(frame, 0) and np.sum(frame, 1) of every uint16 / int16 frame in one read of it, the sums
  * FieldAnalysis._determine_center hands to SingleProfile (pylinac/field_analysis.py:488-506).  d_cols int64 [n][w] (zeroed here),

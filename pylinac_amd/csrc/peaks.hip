@@ -75,21 +75,16 @@ colparts_profile_fwxm_kernel(const uint32_t* __restrict__ parts, int bands, int 
   __shared__ double s_red[2 * (kThreads / PL_WAVE)];
   __shared__ int s_cnt;
   const int64_t frame = blockIdx.x;
-  const int tid = threadIdx.x;
   const uint32_t* pf = parts + frame * (int64_t)bands * w;
-  double* prof = profile + frame * (int64_t)w;
-  for (int i = tid; i < w; i += kThreads) {
-    unsigned long long cs = 0;
-    for (int b = 0; b < bands; ++b) cs += pf[(size_t)b * w + i];
-    prof[i] = (double)cs / (double)h;               // np.mean of integers: float64 sum / count
-  }
-  __syncthreads();                                  // the profile row (global memory) is this workgroup's own
   const PeakLds L{smem_all, &scan, s_red, &s_cnt};
-  find_peaks_profile<STAGE, kThreads>(prof, w, prm.region_lo, prm.region_hi, prm, cap, maxc, L, tid, d_count + frame,
-                                      d_idx + frame * cap, d_lb + frame * cap, d_rb + frame * cap,
-                                      d_props + frame * 6 * (int64_t)cap, d_status + frame);
-  __syncthreads();
-  if (tid == 0) fwxm_record_one(d_count[frame], d_idx + frame * cap, d_props + frame * 6 * (int64_t)cap, cap, fwxm + frame * 8);
+  profile_fwxm_frame<STAGE>(
+      [&](int i) {
+        unsigned long long cs = 0;
+        for (int b = 0; b < bands; ++b) cs += pf[(size_t)b * w + i];
+        return cs;
+      },
+      w, h, prm, cap, maxc, L, (int)threadIdx.x, profile + frame * (int64_t)w, d_count + frame, d_idx + frame * cap,
+      d_lb + frame * cap, d_rb + frame * cap, d_props + frame * 6 * (int64_t)cap, d_status + frame, fwxm + frame * 8);
 }
 
 // CTP528CP504.mtf's searches (pylinac/ct.py:1511-1544) for every (profile, line-pair region) pair in ONE launch, a wave per
@@ -290,11 +285,9 @@ extern "C" int pl_colparts_profile_fwxm(const uint32_t* d_parts, int64_t n, int 
   const int lo = params->region_lo < 0 ? 0 : params->region_lo;
   const int hi = params->region_hi > w ? w : params->region_hi;
   const int m = hi > lo ? hi - lo : 0;
-  int maxc = m / 2 + 1;
-  if (maxc > kMaxCand) maxc = kMaxCand;
   const bool stage_x = m <= kStageMax;
-  size_t lds = (size_t)maxc * (8 + 8 + 4 * 4) + 8 + (stage_x ? (size_t)m * 8 : 0);
-  lds = (lds + 15) & ~(size_t)15;
+  int maxc;
+  const size_t lds = peak_search_lds(m, stage_x, &maxc);
   static std::atomic<bool> attr_set{false};
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute((const void*)colparts_profile_fwxm_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -445,4 +445,32 @@ __device__ __forceinline__ void fwxm_record_one(int c, const int32_t* __restrict
   o[7] = (r > l ? r : l) - (r < l ? r : l);
 }
 
+// The tail of the EPID step for ONE frame, by one workgroup of kPkThreads lanes (all of them call it): colsum(i) = the
+// thresholded frame's integer sum of column i -> np.mean(frame, 0) (pylinac/picketfence.py:747-750: float64 sum of integers /
+// count) into `prof` -> find_peaks on that row -> the FWXM record.  The frame's output rows are passed already offset.
+template <bool STAGE, typename ColSum>
+__device__ __forceinline__ void profile_fwxm_frame(ColSum colsum, int w, int h, const pl_peak_params prm, int cap, int maxc,
+                                                   const PeakLds L, int tid, double* __restrict__ prof, int32_t* __restrict__ o_count,
+                                                   int32_t* __restrict__ o_idx, int32_t* __restrict__ o_lb, int32_t* __restrict__ o_rb,
+                                                   double* __restrict__ o_p, int32_t* __restrict__ o_status, double* __restrict__ fwxm) {
+  for (int i = tid; i < w; i += kPkThreads) {
+    const unsigned long long cs = colsum(i);
+    prof[i] = (double)cs / (double)h;               // np.mean of integers: float64 sum / count
+  }
+  __syncthreads();                                  // the profile row (global memory) is this workgroup's own
+  find_peaks_profile<STAGE, kPkThreads>(prof, w, prm.region_lo, prm.region_hi, prm, cap, maxc, L, tid, o_count, o_idx, o_lb, o_rb,
+                                        o_p, o_status);
+  __syncthreads();
+  if (tid == 0) fwxm_record_one(*o_count, o_idx, o_p, cap, fwxm);
+}
+
+// LDS of a kPkThreads-lane search of a region of m samples: the candidate tables (+ the staged region); -> bytes, *maxc
+static inline size_t peak_search_lds(int m, bool stage_x, int* maxc) {
+  int c = m / 2 + 1;
+  if (c > kMaxCand) c = kMaxCand;
+  *maxc = c;
+  const size_t lds = (size_t)c * (8 + 8 + 4 * 4) + 8 + (stage_x ? (size_t)m * 8 : 0);
+  return (lds + 15) & ~(size_t)15;
+}
+
 }  // namespace

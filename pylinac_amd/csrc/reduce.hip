@@ -15,6 +15,7 @@
 // band, one uint64 atomic per column/band.
 #include "pl_common.h"
 #include "median3_rows.h"
+#include "peaks_device.h"
 
 namespace {
 
@@ -152,14 +153,13 @@ threshold_colsum_kernel(const unsigned short* __restrict__ in, unsigned short* _
 // (32 rows) of the band; the four waves' column sums meet in LDS and leave as one 64-bit atomic per column.
 constexpr int kMtRows = 32;                        // rows per wave: two halo rows are re-read per wave
 constexpr int kMtWaves = kBandRows / kMtRows;      // 4
-// PARTS: the band's column sums are STORED as uint32 parts[frame][band][column] (128 rows x 65535 < 2^32) instead of added to
-// colsum[frame][column] with 64-bit atomics -- no zeroed table, no atomics; pl_colparts_profile_fwxm adds the bands up.
-template <bool PARTS>
-__global__ void __launch_bounds__(kMtWaves * PL_WAVE)
-median3_threshold_colsum_kernel(const unsigned short* __restrict__ in, unsigned short* __restrict__ out, int h, int w, int bands,
-                                int col_groups, const int32_t* __restrict__ thr, unsigned long long* __restrict__ colsum,
-                                uint32_t* __restrict__ parts) {
-  __shared__ unsigned s_cs[PL_WAVE * 8];
+struct MtTile { size_t frame; int band, cg; };
+
+// The pixel work of one workgroup: thresholded medians stored, the four waves' column sums of the tile met in s_cs (complete
+// and visible to every lane on return); -> which tile of which frame this workgroup had.
+__device__ __forceinline__ MtTile median3_threshold_tile(const unsigned short* __restrict__ in, unsigned short* __restrict__ out,
+                                                         int h, int w, int bands, int col_groups, const int32_t* __restrict__ thr,
+                                                         unsigned* s_cs) {
   unsigned id = pl_xcd_remap(blockIdx.x, gridDim.x);
   const int cg = id % col_groups;
   id /= col_groups;
@@ -191,14 +191,80 @@ median3_threshold_colsum_kernel(const unsigned short* __restrict__ in, unsigned 
     for (int k = 0; k < 8; ++k) atomicAdd(&s_cs[lane * 8 + k], s[k]);     // 32 rows x 65535 per wave, 4 waves: < 2^32
   }
   __syncthreads();
+  return MtTile{frame, band, cg};
+}
+
+// PARTS: the band's column sums are STORED as uint32 parts[frame][band][column] (128 rows x 65535 < 2^32) instead of added to
+// colsum[frame][column] with 64-bit atomics -- no zeroed table, no atomics; pl_colparts_profile_fwxm adds the bands up.
+template <bool PARTS>
+__global__ void __launch_bounds__(kMtWaves * PL_WAVE)
+median3_threshold_colsum_kernel(const unsigned short* __restrict__ in, unsigned short* __restrict__ out, int h, int w, int bands,
+                                int col_groups, const int32_t* __restrict__ thr, unsigned long long* __restrict__ colsum,
+                                uint32_t* __restrict__ parts) {
+  __shared__ unsigned s_cs[PL_WAVE * 8];
+  const MtTile t = median3_threshold_tile(in, out, h, w, bands, col_groups, thr, s_cs);
   if (PARTS) {
-    uint32_t* ps = parts + (frame * (size_t)bands + band) * (size_t)w + (size_t)cg * PL_WAVE * 8;
+    uint32_t* ps = parts + (t.frame * (size_t)bands + t.band) * (size_t)w + (size_t)t.cg * PL_WAVE * 8;
     for (int i = threadIdx.x; i < PL_WAVE * 8; i += kMtWaves * PL_WAVE)
-      if (cg * PL_WAVE * 8 + i < w) ps[i] = s_cs[i];
+      if (t.cg * PL_WAVE * 8 + i < w) ps[i] = s_cs[i];
   } else {
-    unsigned long long* cs = colsum + frame * (size_t)w + (size_t)cg * PL_WAVE * 8;
+    unsigned long long* cs = colsum + t.frame * (size_t)w + (size_t)t.cg * PL_WAVE * 8;
     for (int i = threadIdx.x; i < PL_WAVE * 8; i += kMtWaves * PL_WAVE)
-      if (cg * PL_WAVE * 8 + i < w) atomicAdd(cs + i, (unsigned long long)s_cs[i]);
+      if (t.cg * PL_WAVE * 8 + i < w) atomicAdd(cs + i, (unsigned long long)s_cs[i]);
+  }
+}
+
+// The same pass with the REST of the EPID step behind it, frame by frame, in the same launch: the workgroup that finishes a
+// frame LAST turns the frame's column sums into the mean profile, searches its peak and writes the FWXM record and the record
+// row (profile_fwxm_frame: what pl_colsum_to_mean -> pl_find_peaks -> pl_fwxm_record do), while the other workgroups are still
+// thresholding later frames.  kMtWaves * PL_WAVE == kPkThreads: the search is written for exactly this workgroup.
+//
+// Hand-over of the column sums between workgroups (any XCD), no fences -- every access to the shared words is a device-scope
+// atomic, as in otsu16_window_kernel's merge: ws[frame][0 .. w) takes the tiles' sums by RETURNING 64-bit adds whose values are
+// consumed before the barrier, so every add of the workgroup has been performed when thread 0 takes the frame's arrival ticket
+// ws[frame][w]; the workgroup whose ticket is the last of bands x col_groups reads each sum with an exchange that puts the zero
+// back, and zeroes the ticket: the workspace is all zero again when the launch ends.
+template <bool STAGE>
+__global__ void __launch_bounds__(kMtWaves * PL_WAVE)
+median3_threshold_tail_kernel(const unsigned short* __restrict__ in, unsigned short* __restrict__ out, int h, int w, int bands,
+                              int col_groups, const int32_t* __restrict__ thr, unsigned long long* __restrict__ ws,
+                              pl_peak_params prm, int cap, int maxc, double* __restrict__ profile, int32_t* __restrict__ d_count,
+                              int32_t* __restrict__ d_idx, int32_t* __restrict__ d_lb, int32_t* __restrict__ d_rb,
+                              double* __restrict__ d_props, int32_t* __restrict__ d_status, double* __restrict__ fwxm,
+                              double* __restrict__ record) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
+  __shared__ unsigned s_cs[PL_WAVE * 8];
+  __shared__ Scan scan;
+  __shared__ double s_red[2 * (kPkThreads / PL_WAVE)];
+  __shared__ int s_cnt, s_last;
+  static_assert(kMtWaves * PL_WAVE == kPkThreads, "the peak search is written for this workgroup size");
+  const MtTile t = median3_threshold_tile(in, out, h, w, bands, col_groups, thr, s_cs);
+  unsigned long long* cs = ws + t.frame * (size_t)(w + 1);
+  unsigned* ticket = reinterpret_cast<unsigned*>(cs + w);
+  unsigned seen = 0;
+  for (int i = threadIdx.x; i < PL_WAVE * 8; i += kMtWaves * PL_WAVE) {
+    const int col = t.cg * PL_WAVE * 8 + i;
+    const unsigned c = s_cs[i];
+    if (col < w && c) seen |= atomicAdd(cs + col, (unsigned long long)c) == ~0ull ? 1u : 0u;   // RETURNING: the wave waits for its adds
+  }
+  // (a column sum cannot reach 2^64 - 1: `seen` stays 0; it exists so that the returned values are consumed before the barrier)
+  if (seen) s_last = 2;
+  __syncthreads();
+  if (threadIdx.x == 0) s_last = atomicAdd(ticket, 1u) == (unsigned)(bands * col_groups - 1) ? 1 : 0;
+  __syncthreads();
+  if (s_last == 0) return;                                 // not the last workgroup of this frame
+  if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int64_t frame = (int64_t)t.frame;
+  const PeakLds L{smem_all, &scan, s_red, &s_cnt};
+  double* fw = fwxm + frame * 8;
+  profile_fwxm_frame<STAGE>([&](int i) { return atomicExch(cs + i, 0ull); }, w, h, prm, cap, maxc, L, (int)threadIdx.x,
+                            profile + frame * (int64_t)w, d_count + frame, d_idx + frame * cap, d_lb + frame * cap,
+                            d_rb + frame * cap, d_props + frame * 6 * (int64_t)cap, d_status + frame, fw);
+  if (threadIdx.x == 0) {                                  // the lane that wrote fw
+    double* rec = record + frame * 9;
+    rec[0] = (double)thr[frame];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) rec[1 + k] = fw[k];
   }
 }
 
@@ -390,6 +456,65 @@ extern "C" int pl_median3_threshold_colparts_u16(const uint16_t* in, uint16_t* o
   hipLaunchKernelGGL(median3_threshold_colsum_kernel<true>, dim3((unsigned)(n * bands * col_groups)), dim3(kMtWaves * PL_WAVE), 0,
                      (hipStream_t)stream, in, out, h, w, bands, col_groups, d_thr, (unsigned long long*)nullptr, d_parts);
   return pl_check_launch("pl_median3_threshold_colparts_u16");
+}
+
+// smallest dynamic LDS of median3_threshold_tail_kernel's peak search that keeps the pass's three workgroups per CU (133 VGPRs:
+// three waves per SIMD; 3 x (48 KiB + 2.4 KiB of static LDS) < 160 KiB): the region staged in LDS if that fits, the candidate
+// tables alone otherwise; 0 = neither fits (regions beyond 3 000 samples)
+static size_t step_tail_lds(const pl_peak_params* params, int w, bool* stage_x, int* maxc) {
+  const int lo = params->region_lo < 0 ? 0 : params->region_lo;
+  const int hi = params->region_hi > w ? w : params->region_hi;
+  const int m = hi > lo ? hi - lo : 0;
+  constexpr size_t kMax = 48 * 1024;
+  *stage_x = true;
+  size_t lds = peak_search_lds(m, true, maxc);
+  if (lds <= kMax) return lds;
+  *stage_x = false;
+  lds = peak_search_lds(m, false, maxc);
+  return lds <= kMax ? lds : 0;
+}
+
+// 1: pl_median3_threshold_profile_fwxm_u16 takes frames of this shape with these search parameters (16-byte aligned planes
+// assumed); 0: run pl_median3_threshold_colsum_u16 / pl_median2d + pl_threshold_colsum_u16 and the separate tail launches
+extern "C" int pl_median3_threshold_profile_fwxm_covers(int h, int w, const pl_peak_params* params) {
+  bool stage_x;
+  int maxc;
+  return params && pl_median3_rows_covers(nullptr, h, w) && step_tail_lds(params, w, &stage_x, &maxc) != 0 ? 1 : 0;
+}
+
+// median -> threshold -> column sums -> mean profile -> peaks -> FWXM record -> record row in ONE launch: see
+// median3_threshold_tail_kernel.  d_ws uint64[n][w + 1] must be ALL ZERO on entry and is all zero again when the launch has
+// run (zero it once, when it is allocated; nothing else may touch it while a launch is in flight): per frame w column sums and
+// the arrival ticket.
+extern "C" int pl_median3_threshold_profile_fwxm_u16(const uint16_t* in, uint16_t* out, int64_t n, int h, int w, const int32_t* d_thr,
+                                                     const pl_peak_params* params, int cap, double* d_profile, int32_t* d_count,
+                                                     int32_t* d_idx, int32_t* d_left_base, int32_t* d_right_base, double* d_props,
+                                                     int32_t* d_status, double* d_fwxm, double* d_record,
+                                                     unsigned long long* d_ws, void* stream) {
+  PL_REQUIRE(in && out && d_thr && in != out, "null or aliased pointers");
+  PL_REQUIRE(params && d_profile && d_count && d_idx && d_left_base && d_right_base && d_props && d_status && d_fwxm && d_record &&
+             d_ws, "null pointer");
+  PL_REQUIRE(n >= 0 && h > 0 && w > 0 && cap > 0, "bad shape");
+  PL_REQUIRE(params->distance >= 1, "distance must be >= 1");
+  PL_REQUIRE(pl_median3_rows_covers(in, h, w) && (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+             "needs h > 1, width % 8 == 0 and 16-byte aligned frames (run the separate launches otherwise)");
+  bool stage_x;
+  int maxc;
+  const size_t lds = step_tail_lds(params, w, &stage_x, &maxc);
+  PL_REQUIRE(lds != 0, "search region too long for the one-launch form (run the separate launches)");
+  if (n == 0) return PL_OK;
+  const int bands = (int)pl_cdiv(h, kBandRows), col_groups = (int)pl_cdiv(w / 8, PL_WAVE);
+  PL_REQUIRE(n * bands * col_groups <= 0x7fffffffLL, "batch too large");
+  const dim3 grid((unsigned)(n * bands * col_groups)), block(kMtWaves * PL_WAVE);
+  if (stage_x)
+    hipLaunchKernelGGL(median3_threshold_tail_kernel<true>, grid, block, lds, (hipStream_t)stream, in, out, h, w, bands, col_groups,
+                       d_thr, d_ws, *params, cap, maxc, d_profile, d_count, d_idx, d_left_base, d_right_base, d_props, d_status,
+                       d_fwxm, d_record);
+  else
+    hipLaunchKernelGGL(median3_threshold_tail_kernel<false>, grid, block, lds, (hipStream_t)stream, in, out, h, w, bands, col_groups,
+                       d_thr, d_ws, *params, cap, maxc, d_profile, d_count, d_idx, d_left_base, d_right_base, d_props, d_status,
+                       d_fwxm, d_record);
+  return pl_check_launch("pl_median3_threshold_profile_fwxm_u16");
 }
 
 extern "C" int pl_field_center_sums(const void* in, int dtype, int64_t n, int h, int w, unsigned long long* d_cols,

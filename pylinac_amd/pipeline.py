@@ -26,7 +26,14 @@ RECORD_FIELDS = ("otsu_threshold", "n_peaks", "peak_idx", "peak_height", "promin
                  "left_edge", "right_edge", "center", "width")
 
 # stages of the default path (3x3 median on frames of width % 8 == 0); other geometries run the separate entry points
-STAGES = ("gauss2d", "median3_otsu16", "median3_threshold_colsum", "colsum_to_mean", "find_peaks", "fwxm_record")
+STAGES = ("gauss2d", "median3_otsu16", "median3_threshold_tail")
+# the same geometry with EpidPipeline.tail = "separate": the tail as launches of its own (+ a cat for the record)
+STAGES_SEPARATE = ("gauss2d", "median3_otsu16", "median3_threshold_colsum", "colsum_to_mean", "find_peaks", "fwxm_record")
+
+# record tables an EpidPipeline rotates through: the table a step's record() returns is rewritten RECORD_RING steps later (the
+# other fields of a result are rewritten by the very next step).  Deep enough for a loop that keeps the all-gathers of the two
+# previous steps in flight while the next step runs (bench.py, dist.all_gather_records with `pending`).
+RECORD_RING = 4
 
 
 @dataclass
@@ -36,9 +43,13 @@ class EpidResult:
     threshold: torch.Tensor  # int32 [N]       Otsu threshold
     fwxm: torch.Tensor       # float64 [N,8]   ops.fwxm_record fields
     status: torch.Tensor     # int32 [N]       0 = ok (find_peaks capacity status)
+    record_table: torch.Tensor | None = None   # float64 [N,9] written by the step's last launch (tail = "in_launch")
 
     def record(self) -> torch.Tensor:
-        """float64 [N, 9] per-image scalar record (RECORD_FIELDS) -- what is all-gathered."""
+        """float64 [N, 9] per-image scalar record (RECORD_FIELDS) -- what is all-gathered.  The in-launch tail has written it
+        already (nothing is launched here; see RECORD_RING for how long the table lives); the other paths assemble it."""
+        if self.record_table is not None:
+            return self.record_table
         return torch.cat([self.threshold.to(torch.float64)[:, None], self.fwxm], dim=1)
 
 
@@ -51,18 +62,27 @@ class EpidPipeline:
     sigma: float = 5
     median_size: int = 3
     fwxm_height: float = 50
-    # True: per-band column sums + ONE launch for profile -> peaks -> record (pl_colparts_profile_fwxm) instead of memset +
-    # 64-bit atomics + three small launches.  Same results; measured on 256 x 1024^2 (scripts/time_epid_tail.py): 0.7675 ms
-    # per step against 0.760 -- back-to-back launches on one stream cost next to nothing at that size, so the default (None)
-    # turns it on for small batches only, where three launch latencies are a tenth of the step
-    fused_tail: bool | None = None
+    # what follows the threshold + column sums of a 3x3-median frame of width % 8 == 0 (same results, bit for bit):
+    #   "in_launch"  the workgroup that finishes a frame last runs profile -> peaks -> record for it inside the threshold launch
+    #                (pl_median3_threshold_profile_fwxm_u16): no memset, no further launch, record() launches nothing
+    #   "colparts"   per-band column sums + ONE launch for profile -> peaks -> record (pl_colparts_profile_fwxm)
+    #   "separate"   memset + 64-bit atomics + pl_colsum_to_mean, pl_find_peaks, pl_fwxm_record
+    # None = "in_launch" wherever the entry point covers the geometry.  scripts/time_epid_tail.py times the three.
+    tail: str | None = None
     timings: dict = field(default_factory=dict)
 
     def __post_init__(self):
         dev = self.device
         n, h, w = self.n, self.h, self.w
-        if self.fused_tail is None:
-            self.fused_tail = n <= 64
+        self.lib = _lib.load()
+        self.prm = ops.make_peak_params(w, fwxm_height=self.fwxm_height / 100, max_number=1)
+        covered = bool(self.lib.pl_median3_threshold_profile_fwxm_covers(h, w, C.byref(self.prm)))
+        if self.tail is None:
+            self.tail = "in_launch" if covered else "separate"
+        if self.tail not in ("in_launch", "colparts", "separate"):
+            raise ValueError(f"tail = {self.tail!r}: in_launch, colparts or separate")
+        if self.tail == "in_launch" and not covered:
+            raise ValueError("tail = 'in_launch' needs h > 1, w % 8 == 0 and a search region of at most ~3000 samples")
         u16 = dict(dtype=torch.uint16, device=dev)
         self.buf_a = torch.empty((n, h, w), **u16)
         self.buf_b = torch.empty((n, h, w), **u16)
@@ -73,7 +93,6 @@ class EpidPipeline:
         self.vmax = torch.empty(n, dtype=torch.int32, device=dev)
         self.flag = torch.empty(n, dtype=torch.int32, device=dev)
         self.colsum = torch.empty((n, w), dtype=torch.int64, device=dev)
-        self.lib = _lib.load()
         self.bands = -(-h // self.lib.pl_colparts_band_rows())
         self.parts = torch.empty((n, self.bands, w), dtype=torch.int32, device=dev)   # uint32 per-band column sums
         self.profile = torch.empty((n, w), dtype=torch.float64, device=dev)
@@ -87,7 +106,11 @@ class EpidPipeline:
             status=torch.empty(n, dtype=torch.int32, device=dev),
         )
         self.wts, self.host_wts, self.radius = ops._device_weights(self.sigma, dev)
-        self.prm = ops.make_peak_params(w, fwxm_height=self.fwxm_height / 100, max_number=1)
+        # the in-launch tail: its record tables, and per frame w column sums + an arrival ticket that the launch needs ZERO on
+        # entry and leaves zero (zeroed here, once)
+        self.records = torch.empty((RECORD_RING, n, 9), dtype=torch.float64, device=dev)
+        self.tail_ws = torch.zeros((n, w + 1), dtype=torch.int64, device=dev)
+        self._step = 0
 
     def run(self, frames: torch.Tensor, events: dict | None = None, chunks=None) -> EpidResult:
         """One pass over a resident batch.  ``events``: optional {stage: [(start, stop), ...]} sink;
@@ -125,6 +148,9 @@ class EpidPipeline:
 
         # 3x3 median on frames of width % 8 == 0 (torch allocations are 256-byte aligned): consumed on the fly
         fused_median = self.median_size == 3 and h > 1 and w % 8 == 0 and (h * w) % 8 == 0
+        in_launch = fused_median and self.tail == "in_launch"
+        record = self.records[self._step % RECORD_RING] if in_launch else None
+        self._step += 1
 
         def filters(lo, m, stream):
             """Image.filter(sigma, "gaussian"): axis 0 then axis 1 in ONE launch (the axis-0 plane stays in LDS), frames
@@ -153,7 +179,15 @@ class EpidPipeline:
                 stage("median3_otsu16", lambda: lib.pl_median3_otsu16(bp + o, ap + o, U16, m, h, w, None, None, thr + lo * 4,
                                                                       vmin + lo * 4, vmax + lo * 4, flag + lo * 4,
                                                                       hist + lo * 65536 * 4, st), stream)
-                if not self.fused_tail:
+                if in_launch:
+                    # threshold + column sums, and per frame -- by the workgroup that finishes it last, under the thresholding
+                    # of later frames -- mean profile -> peaks -> FWXM record -> record row: the step ends with this launch
+                    stage("median3_threshold_tail", lambda: lib.pl_median3_threshold_profile_fwxm_u16(
+                        bp + o, op + o, m, h, w, thr + lo * 4, C.byref(self.prm), 1, profile + lo * w * 8, cnt + lo * 4,
+                        idx + lo * 4, lb + lo * 4, rb + lo * 4, props + lo * 48, status + lo * 4, fwxm + lo * 64,
+                        record.data_ptr() + lo * 72, self.tail_ws.data_ptr() + lo * (w + 1) * 8, st), stream)
+                    return
+                if self.tail == "separate":
                     stage("median3_threshold_colsum", lambda: lib.pl_median3_threshold_colsum_u16(
                         bp + o, op + o, m, h, w, thr + lo * 4, colsum + lo * w * 8, st), stream)
                     separate_tail()
@@ -187,7 +221,7 @@ class EpidPipeline:
                 done.record(main)
                 self._stage_free.append(done)              # the staging rows may be overwritten once the Gaussian has read them
                 rest(lo, m, main)
-        return EpidResult(self.out, self.profile, self.thr, self.fwxm, self.peaks.status)
+        return EpidResult(self.out, self.profile, self.thr, self.fwxm, self.peaks.status, record)
 
     def run_from_host(self, host_frames: torch.Tensor, chunks: int = 8, events: dict | None = None) -> EpidResult:
         """The step for frames that arrive in (pinned) HOST memory -- what a loader hands over.
