@@ -165,6 +165,13 @@ int pl_otsu16(const void* in, int dtype, int64_t n, int64_t count, const int32_t
 int pl_median3_otsu16(const void* in, void* scratch, int dtype, int64_t n, int h, int w, const int32_t* d_lo,
                       const int32_t* d_hi, int32_t* d_thr, int32_t* d_min, int32_t* d_max, int32_t* d_flag,
                       uint32_t* d_hist, void* stream);
+/* pl_median3_otsu16 of uint16 frames that ALSO leaves, from the medians it computes anyway, d_cellmax uint16
+ * [n][ceil(h / 32)][ceil(w / 64)]: the largest 3x3 median of each cell of 32 rows x 64 columns, for every frame, whichever
+ * kernel tallied it.  pl_median3_threshold_profile_fwxm_cells_u16 consumes it.  PL_ERR_INVALID_ARG for int16 frames and for
+ * frames beyond 2^26 pixels. */
+int pl_median3_otsu16_cells(const void* in, void* scratch, int dtype, int64_t n, int h, int w, const int32_t* d_lo,
+                            const int32_t* d_hi, int32_t* d_thr, int32_t* d_min, int32_t* d_max, int32_t* d_flag,
+                            uint32_t* d_hist, uint16_t* d_cellmax, void* stream);
 /* exact order statistics: out[i][k] = value with 0-based rank d_ranks[k] in frame i
  * (np.percentile call sites: pylinac/core/image.py:899-926, picketfence.py:229-238). */
 int pl_order_stats_from_hist(const uint32_t* d_hist, int dtype, int64_t n, const int64_t* d_ranks,
@@ -858,6 +865,15 @@ int pl_median3_threshold_profile_fwxm_u16(const uint16_t* in, uint16_t* out, int
                                           int32_t* d_idx, int32_t* d_left_base, int32_t* d_right_base, double* d_props,
                                           int32_t* d_status, double* d_fwxm, double* d_record, unsigned long long* d_ws,
                                           void* stream);
+/* The same launch, told what it need not read: d_cellmax uint16 [n][ceil(h / 32)][ceil(w / 64)], every entry >= the largest 3x3
+ * median of its cell of `in` (pl_median3_otsu16_cells of the same plane; 65535 = no knowledge).  Cells whose entry lies below
+ * the frame's threshold are stored as zeros without being read.  Every output as pl_median3_threshold_profile_fwxm_u16, bit
+ * for bit. */
+int pl_median3_threshold_profile_fwxm_cells_u16(const uint16_t* in, uint16_t* out, int64_t n, int h, int w, const int32_t* d_thr,
+                                                const uint16_t* d_cellmax, const pl_peak_params* params, int cap,
+                                                double* d_profile, int32_t* d_count, int32_t* d_idx, int32_t* d_left_base,
+                                                int32_t* d_right_base, double* d_props, int32_t* d_status, double* d_fwxm,
+                                                double* d_record, unsigned long long* d_ws, void* stream);
 int pl_median3_threshold_profile_fwxm_covers(int h, int w, const pl_peak_params* params);
 
 /* ---- FieldAnalysis over a stack of frames (field_analysis.analyze_batch) ---------------------------------------------------

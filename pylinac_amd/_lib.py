@@ -71,6 +71,7 @@ SIGNATURES = {
     "pl_otsu_from_hist": ([_p, _i, _l, _p, _p, _p, _p], C.c_int),
     "pl_otsu16": ([_p, _i, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p], C.c_int),
     "pl_median3_otsu16": ([_p, _p, _i, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p], C.c_int),
+    "pl_median3_otsu16_cells": ([_p, _p, _i, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p], C.c_int),
     "pl_order_stats_from_hist": ([_p, _i, _l, _p, _i, _p, _p], C.c_int),
     "pl_reduce_axis": ([_p, _i, _l, _i, _i, _i, _i, _p, _p], C.c_int),
     "pl_threshold_colsum_u16": ([_p, _p, _l, _i, _i, _p, _p, _p], C.c_int),
@@ -79,6 +80,8 @@ SIGNATURES = {
     "pl_colparts_band_rows": ([], C.c_int),
     "pl_colparts_profile_fwxm": ([_p, _l, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p], C.c_int),
     "pl_median3_threshold_profile_fwxm_u16": ([_p, _p, _l, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p], C.c_int),
+    "pl_median3_threshold_profile_fwxm_cells_u16": ([_p, _p, _l, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+                                                    C.c_int),
     "pl_median3_threshold_profile_fwxm_covers": ([_i, _i, _p], C.c_int),
     "pl_circle_profile": ([_p, _i, _l, _i, _i, _p, _p, _i, _p, _i, _p, _p, _d, _p, _p], C.c_int),
     "pl_circle_profile_combined": ([_p, _i, _l, _i, _i, _p, _l, _l, _i, _p, _p, _i, _p, _i, _p, _p, _d, _p, _p], C.c_int),

@@ -271,15 +271,36 @@ struct OtsuScratch {
 constexpr int kOtsuScratchAt = ((kWinBins + 1) * 4 + 15) & ~15;
 constexpr size_t kOtsuLds = kOtsuScratchAt + sizeof(OtsuScratch);
 
+// ---- cell maxima of the medians (pl_median3_otsu16_cells) --------------------------------------------------------------------
+// A cell = the 32 rows of a tally item x the 64 columns of eight lanes (one 128-byte line per row).  The tally that computes
+// every median anyway leaves each cell's largest one in cellmax[frame][row group][cell column]: the threshold pass behind it
+// (reduce.hip, median3_threshold_tile) skips the loads of cells that lie wholly below the frame's threshold.  uint16 frames
+// only (medians 0 .. 65535).  Both tally kernels record through these two, so a frame's cells are true maxima whichever
+// kernel tallied it.
+__device__ __forceinline__ int cell_max_see(int cm, const int (&m)[8]) {
+  cm = max(max(cm, m[0]), m[1]);                     // (pairs: the compiler forms v_max3)
+  cm = max(max(cm, m[2]), m[3]);
+  cm = max(max(cm, m[4]), m[5]);
+  return max(max(cm, m[6]), m[7]);
+}
+// called by the whole wave; row_cells = the row group's cells at the wave's first column; `cm` of a lane beyond the frame is
+// meaningless and masked here
+__device__ __forceinline__ void cell_max_store(unsigned short* __restrict__ row_cells, int cm, int lane, bool on) {
+  const unsigned g = pl_group8_max(on ? (unsigned)cm : 0u);
+  if (on && (lane & 7) == 0) row_cells[lane >> 3] = (unsigned short)g;
+}
+
 // MED3: the histogram is that of the 3x3 MEDIAN of the frame (h x w, geometry of pl_median3_rows_covers), computed on the
 // fly by pl_median3_rows -- the median plane is never written (the window is still placed from a sample of the raw frame: a
 // median lies between the extrema of its window).  T = short / unsigned short decides how the median compares.
-template <typename T, bool MED3>
+// CELLS (MED3, T = unsigned short): the tally also leaves the cell maxima in cellmax[n][row_groups][ceil(w / 64)].
+template <typename T, bool MED3, bool CELLS>
 __global__ void __launch_bounds__(kHistThreads)
 otsu16_window_kernel(const unsigned short* __restrict__ in, int64_t count, int h, int w, unsigned flip, int bias,
                      const int32_t* __restrict__ lo_hint, const int32_t* __restrict__ hi_hint, int32_t* __restrict__ thr,
                      int32_t* __restrict__ vmin, int32_t* __restrict__ vmax, int32_t* __restrict__ flag, int parts,
-                     uint32_t* __restrict__ merge /* parts > 1: [n][65536] zeroed; flag zeroed too */) {
+                     uint32_t* __restrict__ merge /* parts > 1: [n][65536] zeroed; flag zeroed too */,
+                     unsigned short* __restrict__ cellmax) {
   // ALL of the kernel's LDS is the dynamic block: the bins start at LDS address 0, so a bin's byte offset IS its address
   // (with static arrays in front the compiler spent one add per pixel on the base), the reduction scratch sits behind them
   extern __shared__ __attribute__((aligned(16))) unsigned bins[];  // kWinBins + 1, then OtsuScratch
@@ -371,8 +392,10 @@ otsu16_window_kernel(const unsigned short* __restrict__ in, int64_t count, int h
       const int first_on = __builtin_ctzll(act);
       const unsigned cap4 = on ? 4u * (unsigned)range : 0u;      // lanes beyond the frame add 0 to bin 0
       const unsigned inc = on ? 1u : 0u;
+      int cm = 0;                                    // CELLS: the lane's largest median of this item
       pl_median3_rows<T, kRows, kOtsuAhead>(reinterpret_cast<const T*>(src), h, w, c0, lane, (item / col_waves) * kRows,
                              [&](int, const int (&m)[8]) {
+        if constexpr (CELLS) cm = cell_max_see(cm, m);           // before the flat-wave return: it feeds the maximum too
         // one value in the whole wave (saturated / constant neighbourhoods): ONE atomic of 8 x the lane count -- 512 atomics
         // on one address would serialise
         unsigned spread = 0;
@@ -398,6 +421,11 @@ otsu16_window_kernel(const unsigned short* __restrict__ in, int64_t count, int h
           pl_lds_add_abs(a4, inc);
         }
       });
+      if constexpr (CELLS) {
+        const int cell_cols = (w + 63) / 64;
+        cell_max_store(cellmax + ((size_t)frame * row_groups + item / col_waves) * cell_cols + (item % col_waves) * (PL_WAVE / 8), cm,
+                       lane, on);
+      }
     }
   } else if ((reinterpret_cast<uintptr_t>(src) & 15) == 0) {
     const int64_t nvec = count / 8;
@@ -575,9 +603,11 @@ constexpr size_t kFullLds = kFullBinsBytes + sizeof(FullScratch);
 //     (-65 535 or -65 536 per overflow, never compensated), which the caller tests: exactness is checked, not assumed.
 //   GUARD = true (the frame whose total did not add up: > 65 535 pixels of one value outside flat neighbourhoods): the
 //     15-bit fields with the guard bit described above.
-template <typename T, bool MED3, bool GUARD>
+// CELLS: the frame's cell maxima as well (see cell_max_see), frame_cells = cellmax[frame].
+template <typename T, bool MED3, bool GUARD, bool CELLS>
 __device__ __forceinline__ void full_tally_pass(const unsigned short* __restrict__ src, int64_t count, int h, int w, unsigned flip,
-                                                unsigned* __restrict__ bins, FullScratch& scr) {
+                                                unsigned* __restrict__ bins, FullScratch& scr,
+                                                unsigned short* __restrict__ frame_cells) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   // key = value in the biased domain (0 .. 65535), n = how many pixels of it (1, or a whole wave's worth <= 512: the guard
   // bit leaves room for 32 767 more before a carry, far more than every wave's bulk add landing between the two steps)
@@ -622,8 +652,10 @@ __device__ __forceinline__ void full_tally_pass(const unsigned short* __restrict
       const unsigned long long act = __ballot(on);
       if (act == 0ull) continue;
       const int first_on = __builtin_ctzll(act);
+      int cm = 0;
       pl_median3_rows<T, kRows, kOtsuAhead>(reinterpret_cast<const T*>(src), h, w, c0, lane, (item / col_waves) * kRows,
                              [&](int, const int (&m)[8]) {
+        if constexpr (CELLS) cm = cell_max_see(cm, m);
         // one value in the whole wave (saturated / constant neighbourhoods): one add of the wave's count
         unsigned spread = 0;
 #pragma unroll
@@ -637,22 +669,25 @@ __device__ __forceinline__ void full_tally_pass(const unsigned short* __restrict
 #pragma unroll
         for (int k = 0; k < 8; ++k) tally((unsigned)(m[k] + kSBias));
       });
+      if constexpr (CELLS)
+        cell_max_store(frame_cells + (size_t)(item / col_waves) * ((w + 63) / 64) + (item % col_waves) * (PL_WAVE / 8), cm, lane, on);
     }
   } else {
     for (int64_t i = threadIdx.x; i < count; i += kHistThreads) tally((unsigned)src[i] ^ flip);
   }
 }
 
-template <typename T, bool MED3>
+template <typename T, bool MED3, bool CELLS>
 __global__ void __launch_bounds__(kHistThreads)
 otsu16_full_kernel(const unsigned short* __restrict__ in, int64_t count, int h, int w, unsigned flip, int bias,
                    int32_t* __restrict__ thr, int32_t* __restrict__ vmin, int32_t* __restrict__ vmax,
-                   int32_t* __restrict__ flag) {
+                   int32_t* __restrict__ flag, unsigned short* __restrict__ cellmax) {
   extern __shared__ __attribute__((aligned(16))) unsigned bins[];  // 32 768 dwords = 65 536 fields, then FullScratch
   FullScratch& scr = *reinterpret_cast<FullScratch*>(reinterpret_cast<unsigned char*>(bins) + kFullBinsBytes);
   const int64_t frame = blockIdx.x;
   if (flag[frame] == 0) return;                              // the window kernel finished this frame
   const unsigned short* src = in + frame * count;
+  unsigned short* frame_cells = CELLS ? cellmax + (size_t)frame * ((h + 31) / 32) * ((w + 63) / 64) : nullptr;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   auto clear = [&]() {
     for (int i = threadIdx.x; i < 32768; i += kHistThreads) bins[i] = 0;
@@ -708,7 +743,7 @@ otsu16_full_kernel(const unsigned short* __restrict__ in, int64_t count, int h, 
   bool exact = false;
   if (pl_lds_base(bins) == 0u) {                             // (the fast pass addresses the bins by absolute LDS address)
     clear();
-    full_tally_pass<T, MED3, false>(src, count, h, w, flip, bins, scr);
+    full_tally_pass<T, MED3, false, CELLS>(src, count, h, w, flip, bins, scr, frame_cells);
     __syncthreads();
     totals();
     exact = total.c == (unsigned long long)count;
@@ -716,7 +751,7 @@ otsu16_full_kernel(const unsigned short* __restrict__ in, int64_t count, int h, 
   }
   if (!exact) {                                              // a 16-bit field overflowed: once more with the guard bit
     clear();
-    full_tally_pass<T, MED3, true>(src, count, h, w, flip, bins, scr);
+    full_tally_pass<T, MED3, true, CELLS>(src, count, h, w, flip, bins, scr, frame_cells);
     __syncthreads();
     totals();
   }
@@ -1243,16 +1278,16 @@ extern "C" int pl_order_stats_from_hist(const uint32_t* d_hist, int dtype, int64
 int pl_median3_gated(const void* in, void* out, int is_signed, int64_t n, int h, int w, const int32_t* d_gate, hipStream_t st);
 
 namespace {
-template <typename T, bool MED3>
+template <typename T, bool MED3, bool CELLS = false>
 int otsu16_launch(const void* in, void* scratch, int dtype, int64_t n, int64_t count, int h, int w, const int32_t* d_lo,
                   const int32_t* d_hi, int32_t* d_thr, int32_t* d_min, int32_t* d_max, int32_t* d_flag, uint32_t* d_hist,
-                  hipStream_t st, const char* who) {
+                  hipStream_t st, const char* who, unsigned short* d_cellmax = nullptr) {
   const unsigned flip = dtype == PL_I16 ? 0x8000u : 0u;
   const int bias = dtype == PL_I16 ? 32768 : 0;
   const size_t lds = kOtsuLds;                                  // bins + the spare bin of the branch-free tally + scratch
   static std::atomic<bool> attr{false};                        // one flag per instantiation
   if (!attr) {
-    if (hipFuncSetAttribute((const void*)otsu16_window_kernel<T, MED3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+    if (hipFuncSetAttribute((const void*)otsu16_window_kernel<T, MED3, CELLS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
         hipSuccess) {
       pl_set_error("%s: LDS attribute: %s", who, hipGetErrorString(hipGetLastError()));
       return PL_ERR_HIP;
@@ -1270,24 +1305,29 @@ int otsu16_launch(const void* in, void* scratch, int dtype, int64_t n, int64_t c
     if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, (size_t)n * sizeof(int32_t), st);
     if (e != hipSuccess) { pl_set_error("%s: memset: %s", who, hipGetErrorString(e)); return PL_ERR_HIP; }
   }
-  hipLaunchKernelGGL((otsu16_window_kernel<T, MED3>), dim3((unsigned)(n * parts)), dim3(kHistThreads), lds, st,
-                     (const unsigned short*)in, count, h, w, flip, bias, d_lo, d_hi, d_thr, d_min, d_max, d_flag, parts, d_hist);
+  hipLaunchKernelGGL((otsu16_window_kernel<T, MED3, CELLS>), dim3((unsigned)(n * parts)), dim3(kHistThreads), lds, st,
+                     (const unsigned short*)in, count, h, w, flip, bias, d_lo, d_hi, d_thr, d_min, d_max, d_flag, parts, d_hist,
+                     d_cellmax);
   // frames too wide for the window: the full-range kernel (packed 16-bit counters), every workgroup gated by d_flag; the
   // medians are computed on the fly again for exactly those frames.  (Round 3: gated median plane + two-part histogram +
   // scan, 2.2 x the window kernel's time on a stretched batch.)  Frames beyond 2^26 pixels keep the table path.
   if (count <= (int64_t)kFullEvents * 32768) {
     static std::atomic<bool> attr2{false};
     if (!attr2) {
-      if (hipFuncSetAttribute((const void*)otsu16_full_kernel<T, MED3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFullLds) !=
+      if (hipFuncSetAttribute((const void*)otsu16_full_kernel<T, MED3, CELLS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFullLds) !=
           hipSuccess) {
         pl_set_error("%s: LDS attribute: %s", who, hipGetErrorString(hipGetLastError()));
         return PL_ERR_HIP;
       }
       attr2 = true;
     }
-    hipLaunchKernelGGL((otsu16_full_kernel<T, MED3>), dim3((unsigned)n), dim3(kHistThreads), kFullLds, st, (const unsigned short*)in,
-                       count, h, w, flip, bias, d_thr, d_min, d_max, d_flag);
+    hipLaunchKernelGGL((otsu16_full_kernel<T, MED3, CELLS>), dim3((unsigned)n), dim3(kHistThreads), kFullLds, st, (const unsigned short*)in,
+                       count, h, w, flip, bias, d_thr, d_min, d_max, d_flag, d_cellmax);
     return pl_check_launch(who);
+  }
+  if (CELLS) {                                                   // (the table path below tallies a median PLANE: no cells)
+    pl_set_error("%s: frames beyond 2^26 pixels leave no cell table", who);
+    return PL_ERR_INVALID_ARG;
   }
   const unsigned short* plane = (const unsigned short*)in;
   if (MED3) {
@@ -1338,4 +1378,20 @@ extern "C" int pl_median3_otsu16(const void* in, void* scratch, int dtype, int64
                                           (hipStream_t)stream, "pl_median3_otsu16")
              : otsu16_launch<unsigned short, true>(in, scratch, dtype, n, count, h, w, d_lo, d_hi, d_thr, d_min, d_max, d_flag,
                                                    d_hist, (hipStream_t)stream, "pl_median3_otsu16");
+}
+
+// pl_median3_otsu16 that also leaves the cell maxima of the medians (uint16 frames): see cell_max_see
+extern "C" int pl_median3_otsu16_cells(const void* in, void* scratch, int dtype, int64_t n, int h, int w, const int32_t* d_lo,
+                                       const int32_t* d_hi, int32_t* d_thr, int32_t* d_min, int32_t* d_max, int32_t* d_flag,
+                                       uint32_t* d_hist, uint16_t* d_cellmax, void* stream) {
+  PL_REQUIRE(in && scratch && d_thr && d_flag && d_hist && d_cellmax, "null pointer");
+  PL_REQUIRE(in != scratch, "scratch must be a distinct buffer");
+  PL_REQUIRE((d_lo == nullptr) == (d_hi == nullptr), "give both bounds or neither");
+  PL_REQUIRE(n >= 0 && n <= 0x7fffffffLL / 8 && h > 0 && w > 0, "bad shape");
+  PL_REQUIRE(dtype == PL_U16, "the cell table holds medians of uint16 frames (pl_median3_otsu16 for int16)");
+  PL_REQUIRE(pl_median3_rows_covers(in, h, w) && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0,
+             "needs h > 1, width % 8 == 0 and 16-byte aligned frames (run pl_median2d + pl_otsu16 otherwise)");
+  if (n == 0) return PL_OK;
+  return otsu16_launch<unsigned short, true, true>(in, scratch, dtype, n, (int64_t)h * w, h, w, d_lo, d_hi, d_thr, d_min, d_max,
+                                                   d_flag, d_hist, (hipStream_t)stream, "pl_median3_otsu16_cells", d_cellmax);
 }

@@ -18,8 +18,12 @@
 // `r0` (first output row) must be the same in every lane of the wave: it is moved to a scalar register here, so the row
 // walk -- reflection at the frame's first / last row and the row pointers -- is scalar arithmetic (rounds 1-3 did a general
 // reflect with its integer division, and a 64-bit multiply, per lane and row: ~45 of the 180 vector instructions per row).
+// `load` = false: the lane issues NO load and digests zeros; its medians, and the outer columns of its two neighbours'
+// blocks, are then meaningless -- for callers that know beforehand which lanes' medians they will not use (a lane whose
+// medians ARE used needs `load` in itself and in both neighbours).
 template <typename T, int ROWS, int AHEAD = 4, typename F>
-__device__ __forceinline__ void pl_median3_rows(const T* __restrict__ f, int h, int w, int c0, int lane, int r0_lane, F&& consume) {
+__device__ __forceinline__ void pl_median3_rows(const T* __restrict__ f, int h, int w, int c0, int lane, int r0_lane, F&& consume,
+                                                bool load = true) {
   static_assert(sizeof(T) == 2, "16-bit dtypes");
   const int r0 = __builtin_amdgcn_readfirstlane(r0_lane);
   const bool active = c0 < w;
@@ -35,9 +39,11 @@ __device__ __forceinline__ void pl_median3_rows(const T* __restrict__ f, int h, 
     int rr = r < rm ? r : rm;
     rr = rr > 0 ? rr : 0;
     const char* row = reinterpret_cast<const char*>(f) + (size_t)rr * (size_t)w * 2u;   // scalar
-    Raw x;
-    x.q = *reinterpret_cast<const uint4*>(row + offc);
-    x.e = edge ? (int)*reinterpret_cast<const T*>(row + offe) : 0;
+    Raw x{uint4{0u, 0u, 0u, 0u}, 0};
+    if (load) {
+      x.q = *reinterpret_cast<const uint4*>(row + offc);
+      x.e = edge ? (int)*reinterpret_cast<const T*>(row + offe) : 0;
+    }
     return x;
   };
   int lo[3][8], mi[3][8], hi[3][8];

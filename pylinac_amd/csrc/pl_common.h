@@ -258,6 +258,14 @@ __device__ __forceinline__ unsigned long long pl_group8_sum(unsigned long long v
   return v;
 }
 
+// the same for the maximum (unsigned: a lane the move cannot read contributes 0)
+__device__ __forceinline__ unsigned pl_group8_max(unsigned v) {
+  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true));
+  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true));
+  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, true));
+  return v;
+}
+
 // dispatch a dtype enum onto a template parameter
 #define PL_DISPATCH_DTYPE(dtype, T, ...)                         \
   switch (dtype) {                                               \

@@ -157,9 +157,16 @@ struct MtTile { size_t frame; int band, cg; };
 
 // The pixel work of one workgroup: thresholded medians stored, the four waves' column sums of the tile met in s_cs (complete
 // and visible to every lane on return); -> which tile of which frame this workgroup had.
+// CELLS: cellmax[frame][row group of 32][cell of 64 columns] >= the largest median of the cell (pl_median3_otsu16_cells; a
+// wave's 32 x 512 tile is eight cells, a lane's cell is lane >> 3).  A cell whose maximum lies below the threshold is all zero
+// whatever its medians are: `need` = the cell can hold a survivor.  A wave without a needed cell stores its zeros and reads
+// nothing; otherwise a lane loads when it or a lane next to it needs (a block's first / last median takes a column from the
+// neighbouring lane; the wave's outermost lanes fetch theirs from memory themselves, and every wave loads its own halo rows).
+// What a lane stores is decided by `need` alone, never by a median computed next to a lane that did not load.
+template <bool CELLS>
 __device__ __forceinline__ MtTile median3_threshold_tile(const unsigned short* __restrict__ in, unsigned short* __restrict__ out,
                                                          int h, int w, int bands, int col_groups, const int32_t* __restrict__ thr,
-                                                         unsigned* s_cs) {
+                                                         unsigned* s_cs, const unsigned short* __restrict__ cellmax) {
   unsigned id = pl_xcd_remap(blockIdx.x, gridDim.x);
   const int cg = id % col_groups;
   id /= col_groups;
@@ -175,18 +182,31 @@ __device__ __forceinline__ MtTile median3_threshold_tile(const unsigned short* _
   for (int i = threadIdx.x; i < PL_WAVE * 8; i += kMtWaves * PL_WAVE) s_cs[i] = 0;
   __syncthreads();
   unsigned s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (rg < h) {                                     // wave-uniform
+  bool need = true, load = true;
+  unsigned long long needed = ~0ull;                // the wave's lanes that need
+  if (CELLS && rg < h) {
+    const int cell_cols = (w + 63) / 64, row_groups = (h + kMtRows - 1) / kMtRows;
+    // the same comparison as the pixel test m >= t: a cell whose maximum equals the threshold is needed
+    need = on && (int)cellmax[(frame * row_groups + rg / kMtRows) * cell_cols + (c0 >> 6)] >= t;
+    needed = __ballot(need);
+    load = (((needed << 1) | needed | (needed >> 1)) >> lane) & 1ull;
+  }
+  if (rg < h && needed == 0ull) {                   // wave-uniform: nothing of this tile survives -- zeros, and zero column sums
+    const int r1 = rg + kMtRows < h ? rg + kMtRows : h;
+    if (on)
+      for (int r = rg; r < r1; ++r) *reinterpret_cast<uint4*>(o + (size_t)r * w + c0) = uint4{0u, 0u, 0u, 0u};
+  } else if (rg < h) {                              // wave-uniform
     pl_median3_rows<unsigned short, kMtRows>(f, h, w, c0, lane, rg, [&](int r, const int (&m)[8]) {
       if (!on) return;
       unsigned v[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        v[k] = m[k] >= t ? (unsigned)m[k] : 0u;
+        v[k] = (!CELLS || need) && m[k] >= t ? (unsigned)m[k] : 0u;
         s[k] += v[k];
       }
       *reinterpret_cast<uint4*>(o + (size_t)r * w + c0) =
           uint4{v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)};
-    });
+    }, load);
 #pragma unroll
     for (int k = 0; k < 8; ++k) atomicAdd(&s_cs[lane * 8 + k], s[k]);     // 32 rows x 65535 per wave, 4 waves: < 2^32
   }
@@ -202,7 +222,7 @@ median3_threshold_colsum_kernel(const unsigned short* __restrict__ in, unsigned 
                                 int col_groups, const int32_t* __restrict__ thr, unsigned long long* __restrict__ colsum,
                                 uint32_t* __restrict__ parts) {
   __shared__ unsigned s_cs[PL_WAVE * 8];
-  const MtTile t = median3_threshold_tile(in, out, h, w, bands, col_groups, thr, s_cs);
+  const MtTile t = median3_threshold_tile<false>(in, out, h, w, bands, col_groups, thr, s_cs, nullptr);
   if (PARTS) {
     uint32_t* ps = parts + (t.frame * (size_t)bands + t.band) * (size_t)w + (size_t)t.cg * PL_WAVE * 8;
     for (int i = threadIdx.x; i < PL_WAVE * 8; i += kMtWaves * PL_WAVE)
@@ -224,10 +244,12 @@ median3_threshold_colsum_kernel(const unsigned short* __restrict__ in, unsigned 
 // consumed before the barrier, so every add of the workgroup has been performed when thread 0 takes the frame's arrival ticket
 // ws[frame][w]; the workgroup whose ticket is the last of bands x col_groups reads each sum with an exchange that puts the zero
 // back, and zeroes the ticket: the workspace is all zero again when the launch ends.
-template <bool STAGE>
+// CELLS: the pixel pass skips what the cell table proves to lie below the threshold (median3_threshold_tile).
+template <bool STAGE, bool CELLS>
 __global__ void __launch_bounds__(kMtWaves * PL_WAVE)
 median3_threshold_tail_kernel(const unsigned short* __restrict__ in, unsigned short* __restrict__ out, int h, int w, int bands,
-                              int col_groups, const int32_t* __restrict__ thr, unsigned long long* __restrict__ ws,
+                              int col_groups, const int32_t* __restrict__ thr, const unsigned short* __restrict__ cellmax,
+                              unsigned long long* __restrict__ ws,
                               pl_peak_params prm, int cap, int maxc, double* __restrict__ profile, int32_t* __restrict__ d_count,
                               int32_t* __restrict__ d_idx, int32_t* __restrict__ d_lb, int32_t* __restrict__ d_rb,
                               double* __restrict__ d_props, int32_t* __restrict__ d_status, double* __restrict__ fwxm,
@@ -238,7 +260,7 @@ median3_threshold_tail_kernel(const unsigned short* __restrict__ in, unsigned sh
   __shared__ double s_red[2 * (kPkThreads / PL_WAVE)];
   __shared__ int s_cnt, s_last;
   static_assert(kMtWaves * PL_WAVE == kPkThreads, "the peak search is written for this workgroup size");
-  const MtTile t = median3_threshold_tile(in, out, h, w, bands, col_groups, thr, s_cs);
+  const MtTile t = median3_threshold_tile<CELLS>(in, out, h, w, bands, col_groups, thr, s_cs, cellmax);
   unsigned long long* cs = ws + t.frame * (size_t)(w + 1);
   unsigned* ticket = reinterpret_cast<unsigned*>(cs + w);
   unsigned seen = 0;
@@ -482,6 +504,44 @@ extern "C" int pl_median3_threshold_profile_fwxm_covers(int h, int w, const pl_p
   return params && pl_median3_rows_covers(nullptr, h, w) && step_tail_lds(params, w, &stage_x, &maxc) != 0 ? 1 : 0;
 }
 
+namespace {
+template <bool CELLS>
+int step_tail_launch(const char* who, const uint16_t* in, uint16_t* out, int64_t n, int h, int w, const int32_t* d_thr,
+                     const uint16_t* d_cellmax, const pl_peak_params* params, int cap, double* d_profile, int32_t* d_count,
+                     int32_t* d_idx, int32_t* d_left_base, int32_t* d_right_base, double* d_props, int32_t* d_status,
+                     double* d_fwxm, double* d_record, unsigned long long* d_ws, void* stream) {
+  auto bad = [&](const char* msg) {
+    pl_set_error("%s: %s", who, msg);
+    return PL_ERR_INVALID_ARG;
+  };
+  if (!(in && out && d_thr && in != out)) return bad("null or aliased pointers");
+  if (!(params && d_profile && d_count && d_idx && d_left_base && d_right_base && d_props && d_status && d_fwxm && d_record && d_ws &&
+        (d_cellmax || !CELLS)))
+    return bad("null pointer");
+  if (!(n >= 0 && h > 0 && w > 0 && cap > 0)) return bad("bad shape");
+  if (params->distance < 1) return bad("distance must be >= 1");
+  if (!(pl_median3_rows_covers(in, h, w) && (reinterpret_cast<uintptr_t>(out) & 15) == 0))
+    return bad("needs h > 1, width % 8 == 0 and 16-byte aligned frames (run the separate launches otherwise)");
+  bool stage_x;
+  int maxc;
+  const size_t lds = step_tail_lds(params, w, &stage_x, &maxc);
+  if (lds == 0) return bad("search region too long for the one-launch form (run the separate launches)");
+  if (n == 0) return PL_OK;
+  const int bands = (int)pl_cdiv(h, kBandRows), col_groups = (int)pl_cdiv(w / 8, PL_WAVE);
+  if (n * bands * col_groups > 0x7fffffffLL) return bad("batch too large");
+  const dim3 grid((unsigned)(n * bands * col_groups)), block(kMtWaves * PL_WAVE);
+  if (stage_x)
+    hipLaunchKernelGGL((median3_threshold_tail_kernel<true, CELLS>), grid, block, lds, (hipStream_t)stream, in, out, h, w, bands,
+                       col_groups, d_thr, d_cellmax, d_ws, *params, cap, maxc, d_profile, d_count, d_idx, d_left_base, d_right_base,
+                       d_props, d_status, d_fwxm, d_record);
+  else
+    hipLaunchKernelGGL((median3_threshold_tail_kernel<false, CELLS>), grid, block, lds, (hipStream_t)stream, in, out, h, w, bands,
+                       col_groups, d_thr, d_cellmax, d_ws, *params, cap, maxc, d_profile, d_count, d_idx, d_left_base, d_right_base,
+                       d_props, d_status, d_fwxm, d_record);
+  return pl_check_launch(who);
+}
+}  // namespace
+
 // median -> threshold -> column sums -> mean profile -> peaks -> FWXM record -> record row in ONE launch: see
 // median3_threshold_tail_kernel.  d_ws uint64[n][w + 1] must be ALL ZERO on entry and is all zero again when the launch has
 // run (zero it once, when it is allocated; nothing else may touch it while a launch is in flight): per frame w column sums and
@@ -491,30 +551,22 @@ extern "C" int pl_median3_threshold_profile_fwxm_u16(const uint16_t* in, uint16_
                                                      int32_t* d_idx, int32_t* d_left_base, int32_t* d_right_base, double* d_props,
                                                      int32_t* d_status, double* d_fwxm, double* d_record,
                                                      unsigned long long* d_ws, void* stream) {
-  PL_REQUIRE(in && out && d_thr && in != out, "null or aliased pointers");
-  PL_REQUIRE(params && d_profile && d_count && d_idx && d_left_base && d_right_base && d_props && d_status && d_fwxm && d_record &&
-             d_ws, "null pointer");
-  PL_REQUIRE(n >= 0 && h > 0 && w > 0 && cap > 0, "bad shape");
-  PL_REQUIRE(params->distance >= 1, "distance must be >= 1");
-  PL_REQUIRE(pl_median3_rows_covers(in, h, w) && (reinterpret_cast<uintptr_t>(out) & 15) == 0,
-             "needs h > 1, width % 8 == 0 and 16-byte aligned frames (run the separate launches otherwise)");
-  bool stage_x;
-  int maxc;
-  const size_t lds = step_tail_lds(params, w, &stage_x, &maxc);
-  PL_REQUIRE(lds != 0, "search region too long for the one-launch form (run the separate launches)");
-  if (n == 0) return PL_OK;
-  const int bands = (int)pl_cdiv(h, kBandRows), col_groups = (int)pl_cdiv(w / 8, PL_WAVE);
-  PL_REQUIRE(n * bands * col_groups <= 0x7fffffffLL, "batch too large");
-  const dim3 grid((unsigned)(n * bands * col_groups)), block(kMtWaves * PL_WAVE);
-  if (stage_x)
-    hipLaunchKernelGGL(median3_threshold_tail_kernel<true>, grid, block, lds, (hipStream_t)stream, in, out, h, w, bands, col_groups,
-                       d_thr, d_ws, *params, cap, maxc, d_profile, d_count, d_idx, d_left_base, d_right_base, d_props, d_status,
-                       d_fwxm, d_record);
-  else
-    hipLaunchKernelGGL(median3_threshold_tail_kernel<false>, grid, block, lds, (hipStream_t)stream, in, out, h, w, bands, col_groups,
-                       d_thr, d_ws, *params, cap, maxc, d_profile, d_count, d_idx, d_left_base, d_right_base, d_props, d_status,
-                       d_fwxm, d_record);
-  return pl_check_launch("pl_median3_threshold_profile_fwxm_u16");
+  return step_tail_launch<false>(__func__, in, out, n, h, w, d_thr, nullptr, params, cap, d_profile, d_count, d_idx, d_left_base,
+                                 d_right_base, d_props, d_status, d_fwxm, d_record, d_ws, stream);
+}
+
+// The same launch with pl_median3_otsu16_cells' table of the SAME plane: d_cellmax uint16 [n][ceil(h / 32)][ceil(w / 64)], every
+// entry >= the largest 3x3 median of its cell (65535 = never skip).  Same results, bit for bit, every output pixel stored;
+// cells whose maximum lies below the frame's threshold are not read.
+extern "C" int pl_median3_threshold_profile_fwxm_cells_u16(const uint16_t* in, uint16_t* out, int64_t n, int h, int w,
+                                                           const int32_t* d_thr, const uint16_t* d_cellmax,
+                                                           const pl_peak_params* params, int cap, double* d_profile,
+                                                           int32_t* d_count, int32_t* d_idx, int32_t* d_left_base,
+                                                           int32_t* d_right_base, double* d_props, int32_t* d_status,
+                                                           double* d_fwxm, double* d_record, unsigned long long* d_ws,
+                                                           void* stream) {
+  return step_tail_launch<true>(__func__, in, out, n, h, w, d_thr, d_cellmax, params, cap, d_profile, d_count, d_idx, d_left_base,
+                                d_right_base, d_props, d_status, d_fwxm, d_record, d_ws, stream);
 }
 
 extern "C" int pl_field_center_sums(const void* in, int dtype, int64_t n, int h, int w, unsigned long long* d_cols,

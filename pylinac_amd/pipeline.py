@@ -110,6 +110,9 @@ class EpidPipeline:
         # entry and leaves zero (zeroed here, once)
         self.records = torch.empty((RECORD_RING, n, 9), dtype=torch.float64, device=dev)
         self.tail_ws = torch.zeros((n, w + 1), dtype=torch.int64, device=dev)
+        # and what the Otsu stage tells it: the largest median of every cell of 32 rows x 64 columns (cells below the frame's
+        # threshold are stored as zeros without being read)
+        self.cellmax = torch.empty((n, -(-h // 32), -(-w // 64)), dtype=torch.uint16, device=dev)
         self._step = 0
 
     def run(self, frames: torch.Tensor, events: dict | None = None, chunks=None) -> EpidResult:
@@ -176,17 +179,23 @@ class EpidPipeline:
                 # Image.filter(3, "median") is never materialised: the Otsu histogram and the threshold + column sums each
                 # compute the 3x3 medians of the Gaussian plane on the fly (two reads of that plane instead of median write +
                 # two reads of the median plane); buf_a is scratch for frames the one-pass Otsu window cannot hold
-                stage("median3_otsu16", lambda: lib.pl_median3_otsu16(bp + o, ap + o, U16, m, h, w, None, None, thr + lo * 4,
-                                                                      vmin + lo * 4, vmax + lo * 4, flag + lo * 4,
-                                                                      hist + lo * 65536 * 4, st), stream)
                 if in_launch:
-                    # threshold + column sums, and per frame -- by the workgroup that finishes it last, under the thresholding
-                    # of later frames -- mean profile -> peaks -> FWXM record -> record row: the step ends with this launch
-                    stage("median3_threshold_tail", lambda: lib.pl_median3_threshold_profile_fwxm_u16(
-                        bp + o, op + o, m, h, w, thr + lo * 4, C.byref(self.prm), 1, profile + lo * w * 8, cnt + lo * 4,
+                    # the Otsu stage leaves each cell's largest median, and the threshold launch does not read the cells
+                    # that lie below the threshold.  Threshold + column sums, and per frame -- by the workgroup that finishes
+                    # it last, under the thresholding of later frames -- mean profile -> peaks -> FWXM record -> record row:
+                    # the step ends with this launch
+                    cells = self.cellmax.data_ptr() + lo * self.cellmax[0].numel() * 2
+                    stage("median3_otsu16", lambda: lib.pl_median3_otsu16_cells(
+                        bp + o, ap + o, U16, m, h, w, None, None, thr + lo * 4, vmin + lo * 4, vmax + lo * 4, flag + lo * 4,
+                        hist + lo * 65536 * 4, cells, st), stream)
+                    stage("median3_threshold_tail", lambda: lib.pl_median3_threshold_profile_fwxm_cells_u16(
+                        bp + o, op + o, m, h, w, thr + lo * 4, cells, C.byref(self.prm), 1, profile + lo * w * 8, cnt + lo * 4,
                         idx + lo * 4, lb + lo * 4, rb + lo * 4, props + lo * 48, status + lo * 4, fwxm + lo * 64,
                         record.data_ptr() + lo * 72, self.tail_ws.data_ptr() + lo * (w + 1) * 8, st), stream)
                     return
+                stage("median3_otsu16", lambda: lib.pl_median3_otsu16(bp + o, ap + o, U16, m, h, w, None, None, thr + lo * 4,
+                                                                      vmin + lo * 4, vmax + lo * 4, flag + lo * 4,
+                                                                      hist + lo * 65536 * 4, st), stream)
                 if self.tail == "separate":
                     stage("median3_threshold_colsum", lambda: lib.pl_median3_threshold_colsum_u16(
                         bp + o, op + o, m, h, w, thr + lo * 4, colsum + lo * w * 8, st), stream)
