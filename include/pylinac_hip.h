@@ -874,6 +874,22 @@ int pl_median3_threshold_profile_fwxm_cells_u16(const uint16_t* in, uint16_t* ou
                                                 double* d_profile, int32_t* d_count, int32_t* d_idx, int32_t* d_left_base,
                                                 int32_t* d_right_base, double* d_props, int32_t* d_status, double* d_fwxm,
                                                 double* d_record, unsigned long long* d_ws, void* stream);
+/* The cells launch for an `out` that the caller keeps from call to call (a pipeline's own buffer), with the zeros it holds
+ * remembered: d_zeroed uint8 [n][ceil(h / 32)][ceil(w / 64)], d_cellmax's geometry; an entry != 0 says that every pixel of that
+ * cell of `out` is 0 right now.  A cell below the frame's threshold whose entry is set is neither read nor stored; one whose
+ * entry is clear is stored as zeros and its entry set; every other cell is stored and its entry cleared.  reset != 0: no entry
+ * is read -- every pixel is stored as by pl_median3_threshold_profile_fwxm_cells_u16 and the entries are written: the first
+ * call on a table (whose contents may be anything) passes it.  CONTRACT: the table describes exactly the `out` passed with it,
+ * frame for frame.  Whoever writes into `out` by any other route -- another entry point, a copy, a fill -- or pairs the table
+ * with another buffer must pass reset != 0 on the next call; otherwise the pixels of the cells skipped are whatever was left
+ * there.  Same geometry rule (pl_median3_threshold_profile_fwxm_covers) and errors as the cells form; on an `out` that obeys
+ * the contract every output equals that form's, bit for bit. */
+int pl_median3_threshold_profile_fwxm_cells_keep_u16(const uint16_t* in, uint16_t* out, int64_t n, int h, int w,
+                                                     const int32_t* d_thr, const uint16_t* d_cellmax, uint8_t* d_zeroed,
+                                                     int reset, const pl_peak_params* params, int cap, double* d_profile,
+                                                     int32_t* d_count, int32_t* d_idx, int32_t* d_left_base,
+                                                     int32_t* d_right_base, double* d_props, int32_t* d_status, double* d_fwxm,
+                                                     double* d_record, unsigned long long* d_ws, void* stream);
 int pl_median3_threshold_profile_fwxm_covers(int h, int w, const pl_peak_params* params);
 
 /* ---- FieldAnalysis over a stack of frames (field_analysis.analyze_batch) ---------------------------------------------------

@@ -82,6 +82,8 @@ SIGNATURES = {
     "pl_median3_threshold_profile_fwxm_u16": ([_p, _p, _l, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p], C.c_int),
     "pl_median3_threshold_profile_fwxm_cells_u16": ([_p, _p, _l, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
                                                     C.c_int),
+    "pl_median3_threshold_profile_fwxm_cells_keep_u16": (
+        [_p, _p, _l, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p], C.c_int),
     "pl_median3_threshold_profile_fwxm_covers": ([_i, _i, _p], C.c_int),
     "pl_circle_profile": ([_p, _i, _l, _i, _i, _p, _p, _i, _p, _i, _p, _p, _d, _p, _p], C.c_int),
     "pl_circle_profile_combined": ([_p, _i, _l, _i, _i, _p, _l, _l, _i, _p, _p, _i, _p, _i, _p, _p, _d, _p, _p], C.c_int),

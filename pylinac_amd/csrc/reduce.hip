@@ -163,10 +163,27 @@ struct MtTile { size_t frame; int band, cg; };
 // nothing; otherwise a lane loads when it or a lane next to it needs (a block's first / last median takes a column from the
 // neighbouring lane; the wave's outermost lanes fetch theirs from memory themselves, and every wave loads its own halo rows).
 // What a lane stores is decided by `need` alone, never by a median computed next to a lane that did not load.
-template <bool CELLS>
+// KEEP (with CELLS): keep.zeroed[frame][row group][cell] (cellmax's geometry, one byte each) != 0 says that every pixel of the
+// cell of `out` is 0 right now.  A cell that is not needed and whose entry is set is not stored again; one whose entry is clear
+// is stored as zeros and its entry set; a needed cell is stored and its entry cleared (whatever its pixels turn out to be).  A
+// wave without a needed cell and with every entry set issues no load and no store after the table look-ups.  keep.reset != 0:
+// every entry reads as clear (everything is stored, the entries written are right) -- how a table starts.  The cell's first
+// lane, which is in the frame whenever one of the cell is, reads and writes the entry (plain accesses: one wave per entry and
+// launch, stream order carries it to the next launch); the other seven take the verdict from a ballot.
+template <bool KEEP>
+struct MtKeep {};
+template <>
+struct MtKeep<true> {
+  unsigned char* zeroed;
+  int reset;
+};
+
+template <bool CELLS, bool KEEP = false>
 __device__ __forceinline__ MtTile median3_threshold_tile(const unsigned short* __restrict__ in, unsigned short* __restrict__ out,
                                                          int h, int w, int bands, int col_groups, const int32_t* __restrict__ thr,
-                                                         unsigned* s_cs, const unsigned short* __restrict__ cellmax) {
+                                                         unsigned* s_cs, const unsigned short* __restrict__ cellmax,
+                                                         MtKeep<KEEP> keep = {}) {
+  static_assert(CELLS || !KEEP, "the kept-zero table goes with the cell table");
   unsigned id = pl_xcd_remap(blockIdx.x, gridDim.x);
   const int cg = id % col_groups;
   id /= col_groups;
@@ -182,7 +199,7 @@ __device__ __forceinline__ MtTile median3_threshold_tile(const unsigned short* _
   for (int i = threadIdx.x; i < PL_WAVE * 8; i += kMtWaves * PL_WAVE) s_cs[i] = 0;
   __syncthreads();
   unsigned s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  bool need = true, load = true;
+  bool need = true, load = true, store = on;         // KEEP: `store` = the lane's cell of `out` has to be written
   unsigned long long needed = ~0ull;                // the wave's lanes that need
   if (CELLS && rg < h) {
     const int cell_cols = (w + 63) / 64, row_groups = (h + kMtRows - 1) / kMtRows;
@@ -190,14 +207,22 @@ __device__ __forceinline__ MtTile median3_threshold_tile(const unsigned short* _
     need = on && (int)cellmax[(frame * row_groups + rg / kMtRows) * cell_cols + (c0 >> 6)] >= t;
     needed = __ballot(need);
     load = (((needed << 1) | needed | (needed >> 1)) >> lane) & 1ull;
+    if constexpr (KEEP) {
+      const size_t cell = (frame * row_groups + rg / kMtRows) * cell_cols + (c0 >> 6);
+      const bool head = on && (lane & 7) == 0;
+      const bool was = head && !keep.reset && keep.zeroed[cell] != 0;
+      if (head && (keep.reset || was == need)) keep.zeroed[cell] = need ? 0 : 1;
+      const unsigned long long kept = __ballot(was);          // bit 8 * cell: the cell's zeros are in `out` already
+      store = on && (need || !((kept >> (lane & ~7)) & 1ull));
+    }
   }
   if (rg < h && needed == 0ull) {                   // wave-uniform: nothing of this tile survives -- zeros, and zero column sums
     const int r1 = rg + kMtRows < h ? rg + kMtRows : h;
-    if (on)
+    if (KEEP ? store : on)
       for (int r = rg; r < r1; ++r) *reinterpret_cast<uint4*>(o + (size_t)r * w + c0) = uint4{0u, 0u, 0u, 0u};
   } else if (rg < h) {                              // wave-uniform
     pl_median3_rows<unsigned short, kMtRows>(f, h, w, c0, lane, rg, [&](int r, const int (&m)[8]) {
-      if (!on) return;
+      if (KEEP ? !store : !on) return;
       unsigned v[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
@@ -245,7 +270,9 @@ median3_threshold_colsum_kernel(const unsigned short* __restrict__ in, unsigned 
 // ws[frame][w]; the workgroup whose ticket is the last of bands x col_groups reads each sum with an exchange that puts the zero
 // back, and zeroes the ticket: the workspace is all zero again when the launch ends.
 // CELLS: the pixel pass skips what the cell table proves to lie below the threshold (median3_threshold_tile).
-template <bool STAGE, bool CELLS>
+// KEEP: and does not store again the zeros that `keep`'s table says are in `out` already.
+// (a pack of nothing, or of the one MtKeep<true>: without it the kernel's arguments are what they were)
+template <bool STAGE, bool CELLS, typename... KEEP>
 __global__ void __launch_bounds__(kMtWaves * PL_WAVE)
 median3_threshold_tail_kernel(const unsigned short* __restrict__ in, unsigned short* __restrict__ out, int h, int w, int bands,
                               int col_groups, const int32_t* __restrict__ thr, const unsigned short* __restrict__ cellmax,
@@ -253,14 +280,14 @@ median3_threshold_tail_kernel(const unsigned short* __restrict__ in, unsigned sh
                               pl_peak_params prm, int cap, int maxc, double* __restrict__ profile, int32_t* __restrict__ d_count,
                               int32_t* __restrict__ d_idx, int32_t* __restrict__ d_lb, int32_t* __restrict__ d_rb,
                               double* __restrict__ d_props, int32_t* __restrict__ d_status, double* __restrict__ fwxm,
-                              double* __restrict__ record) {
+                              double* __restrict__ record, KEEP... keep) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
   __shared__ unsigned s_cs[PL_WAVE * 8];
   __shared__ Scan scan;
   __shared__ double s_red[2 * (kPkThreads / PL_WAVE)];
   __shared__ int s_cnt, s_last;
   static_assert(kMtWaves * PL_WAVE == kPkThreads, "the peak search is written for this workgroup size");
-  const MtTile t = median3_threshold_tile<CELLS>(in, out, h, w, bands, col_groups, thr, s_cs, cellmax);
+  const MtTile t = median3_threshold_tile<CELLS, sizeof...(KEEP) != 0>(in, out, h, w, bands, col_groups, thr, s_cs, cellmax, keep...);
   unsigned long long* cs = ws + t.frame * (size_t)(w + 1);
   unsigned* ticket = reinterpret_cast<unsigned*>(cs + w);
   unsigned seen = 0;
@@ -505,11 +532,11 @@ extern "C" int pl_median3_threshold_profile_fwxm_covers(int h, int w, const pl_p
 }
 
 namespace {
-template <bool CELLS>
+template <bool CELLS, bool KEEP = false>
 int step_tail_launch(const char* who, const uint16_t* in, uint16_t* out, int64_t n, int h, int w, const int32_t* d_thr,
                      const uint16_t* d_cellmax, const pl_peak_params* params, int cap, double* d_profile, int32_t* d_count,
                      int32_t* d_idx, int32_t* d_left_base, int32_t* d_right_base, double* d_props, int32_t* d_status,
-                     double* d_fwxm, double* d_record, unsigned long long* d_ws, void* stream) {
+                     double* d_fwxm, double* d_record, unsigned long long* d_ws, void* stream, MtKeep<KEEP> keep = {}) {
   auto bad = [&](const char* msg) {
     pl_set_error("%s: %s", who, msg);
     return PL_ERR_INVALID_ARG;
@@ -518,6 +545,8 @@ int step_tail_launch(const char* who, const uint16_t* in, uint16_t* out, int64_t
   if (!(params && d_profile && d_count && d_idx && d_left_base && d_right_base && d_props && d_status && d_fwxm && d_record && d_ws &&
         (d_cellmax || !CELLS)))
     return bad("null pointer");
+  if constexpr (KEEP)
+    if (!keep.zeroed) return bad("null pointer");
   if (!(n >= 0 && h > 0 && w > 0 && cap > 0)) return bad("bad shape");
   if (params->distance < 1) return bad("distance must be >= 1");
   if (!(pl_median3_rows_covers(in, h, w) && (reinterpret_cast<uintptr_t>(out) & 15) == 0))
@@ -530,7 +559,16 @@ int step_tail_launch(const char* who, const uint16_t* in, uint16_t* out, int64_t
   const int bands = (int)pl_cdiv(h, kBandRows), col_groups = (int)pl_cdiv(w / 8, PL_WAVE);
   if (n * bands * col_groups > 0x7fffffffLL) return bad("batch too large");
   const dim3 grid((unsigned)(n * bands * col_groups)), block(kMtWaves * PL_WAVE);
-  if (stage_x)
+  if constexpr (KEEP) {
+    if (stage_x)
+      hipLaunchKernelGGL((median3_threshold_tail_kernel<true, CELLS, MtKeep<true>>), grid, block, lds, (hipStream_t)stream, in, out, h,
+                         w, bands, col_groups, d_thr, d_cellmax, d_ws, *params, cap, maxc, d_profile, d_count, d_idx, d_left_base,
+                         d_right_base, d_props, d_status, d_fwxm, d_record, keep);
+    else
+      hipLaunchKernelGGL((median3_threshold_tail_kernel<false, CELLS, MtKeep<true>>), grid, block, lds, (hipStream_t)stream, in, out,
+                         h, w, bands, col_groups, d_thr, d_cellmax, d_ws, *params, cap, maxc, d_profile, d_count, d_idx, d_left_base,
+                         d_right_base, d_props, d_status, d_fwxm, d_record, keep);
+  } else if (stage_x)
     hipLaunchKernelGGL((median3_threshold_tail_kernel<true, CELLS>), grid, block, lds, (hipStream_t)stream, in, out, h, w, bands,
                        col_groups, d_thr, d_cellmax, d_ws, *params, cap, maxc, d_profile, d_count, d_idx, d_left_base, d_right_base,
                        d_props, d_status, d_fwxm, d_record);
@@ -567,6 +605,21 @@ extern "C" int pl_median3_threshold_profile_fwxm_cells_u16(const uint16_t* in, u
                                                            void* stream) {
   return step_tail_launch<true>(__func__, in, out, n, h, w, d_thr, d_cellmax, params, cap, d_profile, d_count, d_idx, d_left_base,
                                 d_right_base, d_props, d_status, d_fwxm, d_record, d_ws, stream);
+}
+
+// The cells launch on an `out` whose zeros are remembered: d_zeroed uint8 [n][ceil(h / 32)][ceil(w / 64)] != 0 = the cell of
+// `out` is all zero; such a cell is not stored again while it stays below the threshold.  reset != 0: the table is not read
+// (everything is stored, correct entries are written).  Every output as pl_median3_threshold_profile_fwxm_cells_u16.
+extern "C" int pl_median3_threshold_profile_fwxm_cells_keep_u16(const uint16_t* in, uint16_t* out, int64_t n, int h, int w,
+                                                                const int32_t* d_thr, const uint16_t* d_cellmax,
+                                                                uint8_t* d_zeroed, int reset, const pl_peak_params* params,
+                                                                int cap, double* d_profile, int32_t* d_count, int32_t* d_idx,
+                                                                int32_t* d_left_base, int32_t* d_right_base, double* d_props,
+                                                                int32_t* d_status, double* d_fwxm, double* d_record,
+                                                                unsigned long long* d_ws, void* stream) {
+  return step_tail_launch<true, true>(__func__, in, out, n, h, w, d_thr, d_cellmax, params, cap, d_profile, d_count, d_idx,
+                                      d_left_base, d_right_base, d_props, d_status, d_fwxm, d_record, d_ws, stream,
+                                      MtKeep<true>{d_zeroed, reset});
 }
 
 extern "C" int pl_field_center_sums(const void* in, int dtype, int64_t n, int h, int w, unsigned long long* d_cols,

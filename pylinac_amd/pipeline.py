@@ -38,6 +38,9 @@ RECORD_RING = 4
 
 @dataclass
 class EpidResult:
+    """``frames`` is the pipeline's OWN buffer (``EpidPipeline.out``), rewritten by every step -- and with ``keep_zeros`` the
+    next step relies on what this one left in it: cells that were zero and stay below the threshold are not stored again.  Read
+    it freely; a caller who WRITES into it must call ``EpidPipeline.forget_out()`` before the next run."""
     frames: torch.Tensor     # uint16 [N,H,W]  thresholded frames
     profile: torch.Tensor    # float64 [N,W]   column-mean profile
     threshold: torch.Tensor  # int32 [N]       Otsu threshold
@@ -69,6 +72,10 @@ class EpidPipeline:
     #   "separate"   memset + 64-bit atomics + pl_colsum_to_mean, pl_find_peaks, pl_fwxm_record
     # None = "in_launch" wherever the entry point covers the geometry.  scripts/time_epid_tail.py times the three.
     tail: str | None = None
+    # the "in_launch" step remembers, cell by cell (32 rows x 64 columns), which parts of `out` hold zeros already and does not
+    # store zeros over them again (pl_median3_threshold_profile_fwxm_cells_keep_u16): consecutive batches of EPID fields are zero
+    # in mostly the same places.  False = every pixel is stored every step (the launch without the table).
+    keep_zeros: bool = True
     timings: dict = field(default_factory=dict)
 
     def __post_init__(self):
@@ -113,7 +120,16 @@ class EpidPipeline:
         # and what the Otsu stage tells it: the largest median of every cell of 32 rows x 64 columns (cells below the frame's
         # threshold are stored as zeros without being read)
         self.cellmax = torch.empty((n, -(-h // 32), -(-w // 64)), dtype=torch.uint16, device=dev)
+        # and what the launch tells its next run: which cells of `out` it left all zero.  _zeroed_valid[i]: frame i's entries
+        # describe out[i] (False = the launch is told to ignore and rewrite them)
+        self.zeroed = torch.empty(self.cellmax.shape, dtype=torch.uint8, device=dev)
+        self._zeroed_valid = [False] * n
         self._step = 0
+
+    def forget_out(self) -> None:
+        """Call after writing into ``out`` (= ``EpidResult.frames``) by any route other than ``run``: the next run stores every
+        pixel again instead of trusting the zeros it left there."""
+        self._zeroed_valid = [False] * self.n
 
     def run(self, frames: torch.Tensor, events: dict | None = None, chunks=None) -> EpidResult:
         """One pass over a resident batch.  ``events``: optional {stage: [(start, stop), ...]} sink;
@@ -165,6 +181,10 @@ class EpidPipeline:
         def rest(lo, m, stream):
             """median -> Otsu -> threshold -> column profile -> FWXM record, frames [lo, lo+m)."""
             st, o = stream.cuda_stream, lo * fb
+            # every path below stores into out[lo:lo+m]; only the kept-zero launch leaves entries that describe it afterwards
+            # (so a run with keep_zeros or tail changed in between, or one that raised, is followed by a full store)
+            table_known = all(self._zeroed_valid[lo:lo + m])
+            self._zeroed_valid[lo:lo + m] = [False] * m
 
             def separate_tail():
                 stage("colsum_to_mean", lambda: lib.pl_colsum_to_mean(colsum + lo * w * 8, m, w, h,
@@ -188,10 +208,20 @@ class EpidPipeline:
                     stage("median3_otsu16", lambda: lib.pl_median3_otsu16_cells(
                         bp + o, ap + o, U16, m, h, w, None, None, thr + lo * 4, vmin + lo * 4, vmax + lo * 4, flag + lo * 4,
                         hist + lo * 65536 * 4, cells, st), stream)
-                    stage("median3_threshold_tail", lambda: lib.pl_median3_threshold_profile_fwxm_cells_u16(
-                        bp + o, op + o, m, h, w, thr + lo * 4, cells, C.byref(self.prm), 1, profile + lo * w * 8, cnt + lo * 4,
-                        idx + lo * 4, lb + lo * 4, rb + lo * 4, props + lo * 48, status + lo * 4, fwxm + lo * 64,
-                        record.data_ptr() + lo * 72, self.tail_ws.data_ptr() + lo * (w + 1) * 8, st), stream)
+                    tail_args = (C.byref(self.prm), 1, profile + lo * w * 8, cnt + lo * 4, idx + lo * 4, lb + lo * 4, rb + lo * 4,
+                                 props + lo * 48, status + lo * 4, fwxm + lo * 64, record.data_ptr() + lo * 72,
+                                 self.tail_ws.data_ptr() + lo * (w + 1) * 8, st)
+                    if not self.keep_zeros:
+                        stage("median3_threshold_tail", lambda: lib.pl_median3_threshold_profile_fwxm_cells_u16(
+                            bp + o, op + o, m, h, w, thr + lo * 4, cells, *tail_args), stream)
+                        return
+                    # zeros that the previous run left in `out` are not stored again; a range with a frame whose entries
+                    # are not known to describe `out` (first run, forget_out) is stored in full and its entries rewritten
+                    reset = 0 if table_known else 1
+                    stage("median3_threshold_tail", lambda: lib.pl_median3_threshold_profile_fwxm_cells_keep_u16(
+                        bp + o, op + o, m, h, w, thr + lo * 4, cells, self.zeroed.data_ptr() + lo * self.zeroed[0].numel(), reset,
+                        *tail_args), stream)
+                    self._zeroed_valid[lo:lo + m] = [True] * m
                     return
                 stage("median3_otsu16", lambda: lib.pl_median3_otsu16(bp + o, ap + o, U16, m, h, w, None, None, thr + lo * 4,
                                                                       vmin + lo * 4, vmax + lo * 4, flag + lo * 4,
