@@ -451,7 +451,14 @@ int pl_combine_slices(const void* in, void* d_out, int dtype, int64_t n, int64_t
  * d_count int32[n] (zeroed by the caller before level 0),
  * d_level int32[n] (initialised to -1: first level with a hit), d_done int32[n] (zeroed; set once
  * d_count >= max_number, later calls skip the window), d_status int32[n] (0 ok; 1 label table
- * overflow, 2 > 32 candidate regions, 3 region bbox > 160 px, 4 > 8 features). */
+ * overflow, 2 > 32 candidate regions, 3 region bbox > 160 px, 4 > 8 features).
+ * What 2 and 4 mean for the points (nothing redoes such a window):
+ *   2  at some level more than 32 regions passed the cheap candidate test on (area, bbox).  The FIRST 32 of them in label
+ *      (raster) order were analysed there and the rest of that level was not: a feature behind them is missing from that
+ *      level (a later level still finds it if the sweep goes on and fewer candidates remain), so count, level and points can
+ *      differ from the reference's.  The choice is the same on every run.
+ *   4  the reference found more than 8 features: d_count is 8 and d_xy holds the reference's FIRST eight, in its order.
+ * Slots of d_xy at and past d_count are zero. */
 int pl_features_level(const double* d_sample, const int32_t* d_labels, const int32_t* d_nlabels,
                       const double* d_stats, int max_labels, int64_t n, int h, int w, double dpmm,
                       double radius_mm, double tol_mm, double min_sep_px, int max_number, int level,

@@ -76,34 +76,46 @@ features_level_kernel(const double* __restrict__ sample, const int32_t* __restri
   if (threadIdx.x == 0) { s_ncand = 0; s_nhit = 0; }
   __syncthreads();
   // ---- candidate labels: necessary conditions from (area, bbox) only -----------------------------
-  for (int k = threadIdx.x; k < nl; k += kThreads) {
+  auto is_candidate = [&](int k) -> bool {
     const double* s = st + k * 10;
     const double area = s[0];
-    if (area < 1.0) continue;
+    if (area < 1.0) return false;
     const int r0 = (int)s[1], c0 = (int)s[2], r1 = (int)s[3], c1 = (int)s[4];
     const double bbox_area = (double)(r1 - r0) * (double)(c1 - c0);
     if constexpr (FIELD) {
       const int b = prm.border;
-      if (r0 < b || c0 < b || r1 > h - b || c1 > w - b) continue;    // clear_border(buffer_size = b - 1)
+      if (r0 < b || c0 < b || r1 > h - b || c1 > w - b) return false;  // clear_border(buffer_size = b - 1)
       const double lo_a = (prm.radius_mm - prm.tol_mm) * (prm.min_sep_px - prm.tol_mm);
       const double hi_a = (prm.radius_mm + prm.tol_mm) * (prm.min_sep_px + prm.tol_mm);
-      if (!(area / dp2 < hi_a)) continue;                              // filled_area >= area
-      if (!(bbox_area / dp2 > lo_a)) continue;                         // filled_area <= bbox_area
+      if (!(area / dp2 < hi_a)) return false;                            // filled_area >= area
+      return bbox_area / dp2 > lo_a;                                     // filled_area <= bbox_area
     } else {
-      if (r0 == 0 || c0 == 0 || r1 == h || c1 == w) continue;          // clear_border
-      if (!(area / dp2 < larger)) continue;                            // filled_area >= area
-      if (!(bbox_area / dp2 > smaller)) continue;                      // filled_area <= bbox_area
-      const double y = (double)(r1 - r0), x = (double)(c1 - c0);       // is_symmetric (features.py:7-14)
+      if (r0 == 0 || c0 == 0 || r1 == h || c1 == w) return false;        // clear_border
+      if (!(area / dp2 < larger)) return false;                          // filled_area >= area
+      if (!(bbox_area / dp2 > smaller)) return false;                    // filled_area <= bbox_area
+      const double y = (double)(r1 - r0), x = (double)(c1 - c0);         // is_symmetric (features.py:7-14)
       const double hi = (y * 1.05 > y + 3) ? y * 1.05 : y + 3, lo = (y * 0.95 < y - 3) ? y * 0.95 : y - 3;
-      if (x > hi || x < lo) continue;
-      if (!(area / bbox_area < pi / 4 * 1.2)) continue;                // is_round upper bound needs filled >= area
+      if (x > hi || x < lo) return false;
+      return area / bbox_area < pi / 4 * 1.2;                            // is_round upper bound needs filled >= area
     }
+  };
+  for (int k = threadIdx.x; k < nl; k += kThreads) {
+    if (!is_candidate(k)) continue;
     const int slot = atomicAdd(&s_ncand, 1);
     if (slot < 32) s_cand[slot] = k;
   }
   __syncthreads();
   int ncand = s_ncand;
-  if (ncand > 32) { ncand = 32; if (threadIdx.x == 0) status[img] = 2; }
+  if (ncand > 32) {
+    // more candidates than the table holds (status 2): the slots above were granted in no particular order.  One lane takes
+    // them again in label order: the FIRST 32 candidates are analysed, the rest of this level is not
+    ncand = 32;
+    if (threadIdx.x == 0) {
+      status[img] = 2;
+      int n = 0;
+      for (int k = 0; k < nl && n < 32; ++k) if (is_candidate(k)) s_cand[n++] = k;
+    }
+  }
   // process candidates in label order (the reference iterates regions in label order)
   if (threadIdx.x == 0)
     for (int a = 1; a < ncand; ++a) { int v = s_cand[a], b = a - 1; while (b >= 0 && s_cand[b] > v) { s_cand[b + 1] = s_cand[b]; --b; } s_cand[b + 1] = v; }

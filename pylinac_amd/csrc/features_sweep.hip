@@ -308,24 +308,37 @@ bb_sweep_kernel(const double* __restrict__ sample, const SweepSrc src, int h, in
     }
     __syncthreads();
     // ---- G. candidate roots: necessary conditions from (area, bbox) only (same as features.hip)
-    for (int id = tid; id < nruns; id += kSwThreads) {
-      if (parent[id] != (unsigned)id) continue;
+    auto is_candidate = [&](int id) -> bool {
+      if (parent[id] != (unsigned)id) return false;
       const double area = (double)t_area[id];
       const int r0 = (int)(run_info[id] >> 16), c0 = t_c0[id], r1 = t_r1[id] + 1, c1 = t_c1[id] + 1;   // half-open
       const double bbox_area = (double)(r1 - r0) * (double)(c1 - c0);
-      if (r0 == 0 || c0 == 0 || r1 == h || c1 == w) continue;          // clear_border
-      if (!(area / dp2 < larger)) continue;                            // filled_area >= area
-      if (!(bbox_area / dp2 > smaller)) continue;                      // filled_area <= bbox_area
+      if (r0 == 0 || c0 == 0 || r1 == h || c1 == w) return false;      // clear_border
+      if (!(area / dp2 < larger)) return false;                        // filled_area >= area
+      if (!(bbox_area / dp2 > smaller)) return false;                  // filled_area <= bbox_area
       const double y = (double)(r1 - r0), x = (double)(c1 - c0);       // is_symmetric (features.py:7-14)
       const double hi = (y * 1.05 > y + 3) ? y * 1.05 : y + 3, lo = (y * 0.95 < y - 3) ? y * 0.95 : y - 3;
-      if (x > hi || x < lo) continue;
-      if (!(area / bbox_area < pi / 4 * 1.2)) continue;                // is_round upper bound needs filled >= area
+      if (x > hi || x < lo) return false;
+      return area / bbox_area < pi / 4 * 1.2;                          // is_round upper bound needs filled >= area
+    };
+    for (int id = tid; id < nruns; id += kSwThreads) {
+      if (!is_candidate(id)) continue;
       const int slot = atomicAdd(&s_ncand, 1);
       if (slot < 32) s_cand[slot] = id;
     }
     __syncthreads();
     int ncand = s_ncand;
-    if (ncand > 32) { ncand = 32; if (tid == 0) s_status = 2; }
+    if (ncand > 32) {
+      // more candidates than the table holds (status 2): the slots above were granted in no particular order, so which 32 they
+      // kept differs from run to run.  One lane takes them again in root id order: the FIRST 32 candidates in label order are
+      // analysed, the rest of this level is not
+      ncand = 32;
+      if (tid == 0) {
+        s_status = 2;
+        int n = 0;
+        for (int id = 0; id < nruns && n < 32; ++id) if (is_candidate(id)) s_cand[n++] = id;
+      }
+    }
     if (tid == 0)                                             // label order = raster order of the first pixel = root id order
       for (int a = 1; a < ncand; ++a) { int v = s_cand[a], b = a - 1; while (b >= 0 && s_cand[b] > v) { s_cand[b + 1] = s_cand[b]; --b; } s_cand[b + 1] = v; }
     __syncthreads();

@@ -50,7 +50,12 @@ def find_features_batch(samples: torch.Tensor, dpmm: float, radius_mm: float, ra
     Windows up to 160 x 160 run the whole sweep in one launch (``pl_features_sweep``: one workgroup per window, the
     window resident in LDS); larger windows, and windows the sweep kernel hands back (status 3 / 5: a candidate or a
     level too large for its tables), take the level-by-level path (``level_by_level=True`` forces it).  ``defer=True``
-    leaves windows with status 3 / 5 to the caller (no host synchronisation here)."""
+    leaves windows with status 3 / 5 to the caller (no host synchronisation here).
+
+    Two status words stay with the window, which is not redone.  ``2``: at some level more than 32 regions passed the cheap
+    candidate test; the first 32 in label (raster) order were analysed and the rest of that level was not, so a feature may be
+    missing or come from a later level than the reference's.  ``4``: the reference finds more than 8 features; ``count`` is 8
+    and ``xy`` holds its first eight, in its order.  ``xy`` is zero at and past ``count``."""
     s = ops._frames(samples)
     if s.dtype != torch.float64:
         raise TypeError("find_features_batch needs float64 samples")

@@ -337,6 +337,16 @@ def test_bb_finder_restatement_matches_reference_find_features(golden):
     assert checked > 150
 
 
+def test_bb_region_props_match_skimage_on_shape_zoo(golden):
+    """oracle.region_props_like_skimage (perimeter_like_skimage, convex_area_like_skimage, hole fill, weighted centroid) against
+    scikit-image 0.18.3's own regionprops on the shapes of tests/golden/bb_shapes.npz -- discs of 31 to 67 rows, squares,
+    diamonds, ellipses, rings, crescents, lobed and notched blobs, holes open and closed, blurred and noisy windows -- at every
+    level of the sweep whose mask changes; and ndimage.label + border removal gives scikit-image's region set."""
+    import bb_shape_checks as checks
+
+    checks.check_oracle_pinned(golden("bb_shapes"))
+
+
 def test_spectral_restatements_match_reference(golden):
     """a18: oracle.noise_power_spectrum_2d / radial_average / esf_mtf against the reference's own
     pylinac.core.nps and EdgeSpreadFunctionMTF outputs (numpy pocketfft in both: bit-identical), plus the
