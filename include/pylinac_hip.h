@@ -787,6 +787,28 @@ int pl_pf_measure_f64(const double* in, int64_t n, int h, int w, int orientation
                       const int32_t* d_leaf_lo, const int32_t* d_leaf_hi, int nleaves, int max_rows, double height_threshold,
                       double edge_threshold, const pl_peak_params* fwxm_params, double* d_rec, int32_t* d_status,
                       double* d_prof, int lmax, void* stream);
+/* What PicketFence.analyze computes after its measurement loop, from the position table of pl_pf_measure (one workgroup per
+ * frame, no host round trip): the line of every picket (Picket.get_fit, pylinac/picketfence.py:1881-1899: np.polyfit degree 1),
+ * every leaf's distance from its picket's line in mm (MLCValue.error) and the frame's summary.
+ *   d_position float64 [n][nleaves][cap] (NaN = no measurement), d_status int32 [n][nleaves][cap] (a window takes part when its
+ *   status is 0 and its position is a number), d_picket_count int32 [n]; d_leaf_num int32 / d_leaf_center_px / d_leaf_up_px
+ *   float64 [nleaves]: the leaf's number, its centre and its upper marker coordinate (centre - width_px / 2 *
+ *   leaf_analysis_width_ratio) along the axis the leaves are stacked on; nleaves * cap <= 4096.
+ * Per picket slot p the least-squares line through (leaf_up_px, position) over the slot's measured leaves, in float64 and the
+ * centred form (means, Sxx, Sxy; two passes; sums in a fixed order: a frame's result depends on the frame alone):
+ *   d_fit float64 [n][cap][2] = slope, intercept (np.polyfit order; NaN without a line);
+ *   d_picket_status int32 [n][cap]: 0 ok, 1 slot beyond picket_count, 2 fewer than two measured leaves or Sxx == 0 (no line);
+ *   d_error float64 [n][nleaves][cap] = (position - line(leaf_center_px)) / dpmm, NaN without a measurement or a line;
+ *   d_passed_window uint8 [n][nleaves][cap] = |error| < tolerance;
+ *   d_summary float64 [n][8] = n_measured, max |error|, the leaf NUMBER and the picket slot of the first maximum in leaf-major
+ *   then picket order, np.median(|error|) (exact selection; the mean of the two middle values for an even count), 100 *
+ *   count(|error| < tolerance) / n_measured, passed (1 / 0: every measured window under tolerance), 100 * count(|error| <
+ *   action_tolerance) / n_measured (NaN when action_tolerance is NaN = none).  A frame without a measured window: n_measured
+ *   0, passed 0, NaN elsewhere. */
+int pl_pf_errors(const double* d_position, const int32_t* d_status, const int32_t* d_picket_count, int64_t n, int nleaves,
+                 int cap, const int32_t* d_leaf_num, const double* d_leaf_center_px, const double* d_leaf_up_px, double dpmm,
+                 double tolerance, double action_tolerance, double* d_fit, int32_t* d_picket_status, double* d_error,
+                 uint8_t* d_passed_window, double* d_summary, void* stream);
 /* np.mean(q, 1) -> d_out float64 [n][h] (the leaf profile of LEFT_RIGHT pickets, picketfence.py:749) in numpy's PAIRWISE
  * summation order for the contiguous axis.  The summation tree of a row of w values is laid out by the caller
  * (ops.pairwise_plan): d_leaf_start / d_leaf_len int32 [nleaves] = the leaf blocks (<= 128 values each), d_program int32

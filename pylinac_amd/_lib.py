@@ -121,6 +121,7 @@ SIGNATURES = {
     "pl_scaled_colmean_f64": ([_p, _l, _i, _i, _p, _p, _p, _p], C.c_int),
     "pl_scaled_rowmean_f64": ([_p, _l, _i, _i, _p, _p, _p, _p, _i, _p, _i, _p, _p], C.c_int),
     "pl_pf_measure_f64": ([_p, _l, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p, _p, _i, _p], C.c_int),
+    "pl_pf_errors": ([_p, _p, _p, _l, _i, _i, _p, _p, _p, _d, _d, _d, _p, _p, _p, _p, _p, _p], C.c_int),
     "pl_hill_fit": ([_p, _p, _p, _l, _i, _l, _p, _p, _p, _p, _p], C.c_int),
     "pl_hill_fit_ex": ([_p, _p, _p, _l, _i, _l, _p, _p, _p, _p, _p, _p], C.c_int),
     "pl_hill_windows": ([_p, _p, _l, _i, _p, _p, _i, _p, _p, _i, _d, _i, _p, _p, _p, _p, _p], C.c_int),

@@ -16,6 +16,8 @@
 //                       ground + normalize-to-max of that profile (FWXMProfilePhysical(ground=True,
 //                       normalization=MAX), :1609-1614)
 //   pl_pf_positions     centre + max(approx_idx - spacing/2, 0)    picketfence.py:1624-1627
+//   pl_pf_errors        from the position table: every picket's line (Picket.get_fit :1881-1899), every leaf's error in mm
+//                       (MLCValue.error), max / median / share under tolerance / passed per frame; one workgroup per frame
 // One wave per window; the window's integer pixels are staged in LDS once.
 //
 // The *_f64 entry points take float64 frames instead (a rescaled DICOM series with a fractional slope: what the reference's
@@ -902,4 +904,163 @@ extern "C" int pl_scaled_rowmean_f64(const double* in, int64_t n, int h, int w, 
   PL_REQUIRE(nleaves >= 1 && nleaves <= kRmMaxLeaves && nprog == 2 * nleaves - 1, "a summation tree of 1..256 leaves");
   return scaled_rowmean_launch(in, n, h, w, d_sub, d_div, d_leaf_start, d_leaf_len, nleaves, d_program, nprog, d_out, stream,
                                "pl_scaled_rowmean_f64");
+}
+
+// ---- picket fits, leaf errors and the pass / fail summary from the position table (PicketFence.analyze after the measurement
+// loop: Picket.get_fit picketfence.py:1881-1899, MLCValue.error, max_error / abs_median_error / percent_passing / passed) ------
+//
+// One workgroup per frame, four waves.  The frame's table (at most 4096 windows: 32 KiB of float64) is staged in LDS once,
+// coalesced; a wave owns the picket slots p = wave, wave + 4, ..: lane j owns the leaves j, j + 64, .. of its slot through all
+// three passes (means; Sxx, Sxy about the means; errors), so a table cell is read and overwritten by one lane only and the
+// passes need no barrier between them.  The line is the least-squares line of np.polyfit(up, position, 1) in the centred
+// form (numpy solves a column-scaled least-squares system: the two agree to a few tens of roundings of the position); every
+// sum is a lane's leaves in ascending order followed by the xor butterfly, whose partners add the same two numbers: a frame's
+// result does not depend on anything but the frame.  The summary is taken by the whole workgroup over the staged errors.
+// The median is an exact selection by RANK COUNTING (element i's rank = the number of elements that are smaller, or equal and
+// in front of it): every lane reads the same element at a time, which LDS serves as a broadcast, n^2 / 256 reads per thread --
+// 1 000 for the 500 windows of an EPID frame.  A bitonic sort of the padded table would take 78 barrier-separated passes for
+// 4096 slots and reorder a table the stores below still need in place.
+namespace {
+
+constexpr int kPfErrMaxWindows = 4096;
+constexpr int kPfErrWaves = kThreads / PL_WAVE;
+
+__device__ __forceinline__ double pf_wave_sum(double v) {
+  return pl_wave_reduce(v, [](double a, double b) { return a + b; });
+}
+
+__global__ void __launch_bounds__(kThreads)
+pf_errors_kernel(const double* __restrict__ position, const int32_t* __restrict__ status, const int32_t* __restrict__ picket_count,
+                 int nleaves, int cap, const int32_t* __restrict__ leaf_num, const double* __restrict__ leaf_center,
+                 const double* __restrict__ leaf_up, double dpmm, double tolerance, double action_tolerance,
+                 double* __restrict__ fit, int32_t* __restrict__ picket_status, double* __restrict__ error,
+                 unsigned char* __restrict__ passed_window, double* __restrict__ summary) {
+  __shared__ double s_e[kPfErrMaxWindows];            // positions, then errors (mm); NaN = no measurement
+  __shared__ double s_max[kPfErrWaves], s_mid[2];
+  __shared__ int s_arg[kPfErrWaves], s_cnt[kPfErrWaves][3];
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const size_t frame = blockIdx.x;
+  const int m = nleaves * cap;
+  const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+  const double* pos_f = position + frame * (size_t)m;
+  const int32_t* st_f = status + frame * (size_t)m;
+  for (int i = tid; i < m; i += kThreads) s_e[i] = st_f[i] == 0 ? pos_f[i] : qnan;
+  __syncthreads();
+  int pc = picket_count[frame];
+  pc = pc < 0 ? 0 : (pc > cap ? cap : pc);
+  for (int p = wv; p < cap; p += kPfErrWaves) {                      // wave-uniform
+    // pass 1: the means of the measured leaves' upper marker coordinate and position
+    int n = 0;
+    double sx = 0.0, sy = 0.0;
+    if (p < pc)
+      for (int l = lane; l < nleaves; l += PL_WAVE) {
+        const double y = s_e[l * cap + p];
+        if (y == y) { ++n; sx = sx + leaf_up[l]; sy = sy + y; }
+      }
+    n = pl_wave_reduce(n, [](int a, int b) { return a + b; });
+    sx = pf_wave_sum(sx);
+    sy = pf_wave_sum(sy);
+    const double xm = sx / (double)n, ym = sy / (double)n;
+    // pass 2: the moments about the means
+    double sxx = 0.0, sxy = 0.0;
+    if (n >= 2)
+      for (int l = lane; l < nleaves; l += PL_WAVE) {
+        const double y = s_e[l * cap + p];
+        if (y == y) { const double dx = leaf_up[l] - xm; sxx = sxx + dx * dx; sxy = sxy + dx * (y - ym); }
+      }
+    sxx = pf_wave_sum(sxx);
+    sxy = pf_wave_sum(sxy);
+    const int pst = p >= pc ? 1 : ((n < 2 || !(sxx > 0.0)) ? 2 : 0);
+    const double slope = sxy / sxx;
+    // pass 3: the errors, into the cells the positions came from
+    for (int l = lane; l < nleaves; l += PL_WAVE) {
+      const double y = s_e[l * cap + p];
+      s_e[l * cap + p] = pst == 0 ? (y - (ym + slope * (leaf_center[l] - xm))) / dpmm : qnan;   // (NaN stays NaN)
+    }
+    if (lane == 0) {
+      picket_status[frame * cap + p] = pst;
+      fit[(frame * cap + p) * 2] = pst == 0 ? slope : qnan;
+      fit[(frame * cap + p) * 2 + 1] = pst == 0 ? ym - slope * xm : qnan;       // np.polyfit order: slope, intercept
+    }
+  }
+  __syncthreads();
+  // the table out (coalesced), and the thread's share of the summary: windows i = tid, tid + 256, .. in ascending order, so a
+  // strict comparison keeps the first of equal maxima
+  int cnt = 0, under = 0, under_a = 0, arg = 0x7fffffff;
+  double best = -1.0;
+  for (int i = tid; i < m; i += kThreads) {
+    const double e = s_e[i], a = fabs(e);
+    error[frame * (size_t)m + i] = e;
+    passed_window[frame * (size_t)m + i] = a < tolerance ? 1 : 0;    // (a NaN compares false)
+    if (a == a) {
+      ++cnt;
+      under += a < tolerance ? 1 : 0;
+      under_a += a < action_tolerance ? 1 : 0;
+      if (a > best) { best = a; arg = i; }
+    }
+  }
+  cnt = pl_wave_reduce(cnt, [](int a, int b) { return a + b; });
+  under = pl_wave_reduce(under, [](int a, int b) { return a + b; });
+  under_a = pl_wave_reduce(under_a, [](int a, int b) { return a + b; });
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {                                 // the larger |error|, of equal ones the first window
+    const double ob = __shfl_xor(best, o, 64);
+    const int oa = __shfl_xor(arg, o, 64);
+    if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+  }
+  if (lane == 0) { s_cnt[wv][0] = cnt; s_cnt[wv][1] = under; s_cnt[wv][2] = under_a; s_max[wv] = best; s_arg[wv] = arg; }
+  __syncthreads();
+  cnt = under = under_a = 0;
+  best = -1.0;
+  arg = 0x7fffffff;
+  for (int k = 0; k < kPfErrWaves; ++k) {
+    cnt += s_cnt[k][0]; under += s_cnt[k][1]; under_a += s_cnt[k][2];
+    if (s_max[k] > best || (s_max[k] == best && s_arg[k] < arg)) { best = s_max[k]; arg = s_arg[k]; }
+  }
+  // np.median of the |errors|: the element(s) of rank (cnt - 1) / 2 and cnt / 2
+  const int k_lo = (cnt - 1) >> 1, k_hi = cnt >> 1;
+  for (int i = tid; i < m; i += kThreads) {
+    const double a = fabs(s_e[i]);
+    if (!(a == a)) continue;
+    int rank = 0;
+    for (int j = 0; j < m; ++j) {
+      const double b = fabs(s_e[j]);
+      rank += (b < a || (b == a && j < i)) ? 1 : 0;                  // (a NaN is neither)
+    }
+    if (rank == k_lo) s_mid[0] = a;
+    if (rank == k_hi) s_mid[1] = a;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double* s = summary + frame * 8;
+    const bool any = cnt > 0;
+    s[0] = (double)cnt;
+    s[1] = any ? best : qnan;
+    s[2] = any ? (double)leaf_num[arg / cap] : qnan;
+    s[3] = any ? (double)(arg % cap) : qnan;
+    s[4] = any ? ((cnt & 1) ? s_mid[1] : (s_mid[0] + s_mid[1]) / 2.0) : qnan;
+    s[5] = any ? (100.0 * (double)under) / (double)cnt : qnan;
+    s[6] = any && under == cnt ? 1.0 : 0.0;
+    s[7] = any && action_tolerance == action_tolerance ? (100.0 * (double)under_a) / (double)cnt : qnan;
+  }
+}
+
+}  // namespace
+
+/* picket fits, leaf errors, pass / fail summary: see pylinac_hip.h */
+extern "C" int pl_pf_errors(const double* d_position, const int32_t* d_status, const int32_t* d_picket_count, int64_t n,
+                            int nleaves, int cap, const int32_t* d_leaf_num, const double* d_leaf_center_px,
+                            const double* d_leaf_up_px, double dpmm, double tolerance, double action_tolerance, double* d_fit,
+                            int32_t* d_picket_status, double* d_error, uint8_t* d_passed_window, double* d_summary,
+                            void* stream) {
+  PL_REQUIRE(d_position && d_status && d_picket_count && d_leaf_num && d_leaf_center_px && d_leaf_up_px && d_fit &&
+                 d_picket_status && d_error && d_passed_window && d_summary, "null pointer");
+  PL_REQUIRE(n >= 0 && n <= 0x7fffffffLL && nleaves > 0 && cap > 0, "bad shape");
+  PL_REQUIRE((int64_t)nleaves * cap <= kPfErrMaxWindows, "at most 4096 windows (leaves x picket slots) per frame");
+  PL_REQUIRE(dpmm > 0.0 && tolerance > 0.0, "dpmm and tolerance must be positive");
+  if (n == 0) return PL_OK;
+  hipLaunchKernelGGL(pf_errors_kernel, dim3((unsigned)n), dim3(kThreads), 0, (hipStream_t)stream, d_position, d_status,
+                     d_picket_count, nleaves, cap, d_leaf_num, d_leaf_center_px, d_leaf_up_px, dpmm, tolerance, action_tolerance,
+                     d_fit, d_picket_status, d_error, d_passed_window, d_summary);
+  return pl_check_launch("pl_pf_errors");
 }

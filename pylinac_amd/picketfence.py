@@ -9,9 +9,11 @@ kernels as the float64 quotient ``(a - min) / (max - min)``.  int16 frames and f
 integers go through an exact uint16 bridge; float64 frames with fractional values (a rescaled DICOM
 series) are measured on their own float64 kernels with ``measure_fractional=True``.
 
-The per-dataset post-processing of the reference (dropping leaf rows without the modal number of
-kisses :810-824, per-picket line fits :831-843, error in mm :1701-1718) works on the returned
-``[N, leaves, P]`` positions and stays on the host -- a few thousand flops per image.
+``evaluate_batch`` takes the returned ``[N, leaves, P]`` positions to the numbers a picket-fence user reads -- the line
+fitted through every picket (``Picket.get_fit`` :1881-1899), every leaf's distance from its picket's line in mm
+(``MLCValue.error``), ``max_error`` with its leaf and picket, ``abs_median_error``, ``percent_passing``, ``passed`` -- in one
+launch, one workgroup per frame.  Dropping leaf rows without the modal number of kisses (:810-824) is not built: every
+measured window takes part.
 """
 from __future__ import annotations
 
@@ -208,3 +210,89 @@ def analyze_batch(frames: torch.Tensor, dpmm: float, mlc: str = "MILLENNIUM", nu
         rec = torch.where(bad.unsqueeze(-1), torch.full_like(rec, float("nan")), rec)
     return PFBatchResult([v[0] for v in view], pk_idx, peaks.count, spacing, rec[..., 0], status.view(n, nl, cap),
                          rec[..., 1] if separate_leaves else None, rec[..., 2] if separate_leaves else None)
+
+
+PF_SUMMARY_FIELDS = ("n_measured", "max_error", "max_error_leaf", "max_error_picket", "abs_median_error", "percent_passing",
+                     "passed", "percent_under_action")
+
+
+@dataclass
+class PFErrorsBatch:
+    fit: torch.Tensor            # float64 [N, cap, 2]       slope, intercept of every picket's line (np.polyfit order), px
+    picket_status: torch.Tensor  # int32 [N, cap]            0 ok, 1 slot beyond picket_count, 2 no line (< 2 leaves, Sxx == 0)
+    error: torch.Tensor          # float64 [N, leaves, cap]  position - line at the leaf centre, mm (NaN = none)
+    passed_window: torch.Tensor  # uint8 [N, leaves, cap]    |error| < tolerance
+    summary: torch.Tensor        # float64 [N, 8]            PF_SUMMARY_FIELDS
+    PF_SUMMARY_FIELDS = PF_SUMMARY_FIELDS
+
+
+def leaf_markers(shape, dpmm: float, mlc="MILLENNIUM", orientation: str = "UP_DOWN", leaf_analysis_width_ratio: float = 0.4):
+    """The leaves in view of a frame of ``shape`` with ``analyze_batch``'s arithmetic (``_leaves_in_view``, ``_get_mlc_window``)
+    -> (leaf numbers, leaf_center_px, leaf_up_px): the centre ``across / 2 + center * dpmm`` and the upper marker coordinate
+    ``leaf_center_px - leaf_width_px / 2 * leaf_analysis_width_ratio`` along the axis the leaves are stacked on.  ``mlc``: a
+    bank's name, or a leaf arrangement ``[(number of leaves, width mm), ...]`` as the reference's ``MLCArrangement`` takes."""
+    if orientation not in ("UP_DOWN", "LEFT_RIGHT"):
+        raise ValueError("orientation must be 'UP_DOWN' or 'LEFT_RIGHT'")
+    leaves, centers, widths = mlc_arrangement(MLC_ARRANGEMENTS[mlc] if isinstance(mlc, str) else list(mlc))
+    view = leaves_in_view(tuple(shape), dpmm, leaves, centers, widths, leaf_analysis_width_ratio, orientation)
+    across = shape[1] if orientation == "LEFT_RIGHT" else shape[0]
+    center_px, up_px = [], []
+    for _, center, width in view:
+        leaf_width_px = width * dpmm
+        leaf_center_px = center * dpmm + across / 2
+        center_px.append(leaf_center_px)
+        up_px.append(leaf_center_px - leaf_width_px / 2 * leaf_analysis_width_ratio)
+    return [v[0] for v in view], center_px, up_px
+
+
+def evaluate_batch(result: PFBatchResult, shape, dpmm: float, mlc="MILLENNIUM", orientation: str = "UP_DOWN",
+                   leaf_analysis_width_ratio: float = 0.4, tolerance: float = 0.5,
+                   action_tolerance: float | None = None) -> PFErrorsBatch:
+    """What ``PicketFence.analyze`` computes after its measurement loop, for the ``analyze_batch`` result of frames of
+    ``shape`` (H, W), in one launch and without a synchronisation: per picket the line ``np.polyfit(up, position, 1)`` over
+    the leaves it measured, fitted over the leaf's upper marker coordinate; per window the error in mm, the position minus the
+    line at the leaf's centre over ``dpmm``; per frame one ``summary`` row (``PF_SUMMARY_FIELDS``) -- the record a caller hands
+    to ``dist.all_gather_records``.  The rule reproduces the reference's ``max_error``.  ``abs_median_error``
+    is ``np.median`` of the |errors|, ``percent_passing`` counts |error| < tolerance (strictly), ``passed`` says that every
+    measured window is under tolerance, ``percent_under_action`` is NaN without an ``action_tolerance``; a frame without a
+    measured window has ``n_measured`` 0, ``passed`` 0 and NaN elsewhere.  ``max_error_leaf`` is the leaf NUMBER and
+    ``max_error_picket`` the slot of the first maximum in leaf-major, then picket order (the reference's ``mlc_meas``).
+
+    ``mlc``, ``orientation`` and ``leaf_analysis_width_ratio`` must be those of the ``analyze_batch`` call: the leaves in view
+    must be ``result.leaf_nums`` (ValueError).  A ``separate_leaves`` result is refused: the reference's per-bank errors
+    carry a nominal-gap offset that nothing here pins.  At most 4096 windows (leaves x picket slots) per frame."""
+    if result.left is not None or result.right is not None:
+        raise NotImplementedError("evaluate_batch takes the leaf-pair centres only (separate_leaves=False)")
+    tolerance = float(tolerance)
+    if not tolerance > 0:
+        raise ValueError("tolerance must be positive")
+    if action_tolerance is not None and not float(action_tolerance) < tolerance:
+        raise ValueError("action_tolerance must be lower than tolerance")        # the reference's own rule (picketfence.py:702)
+    nums, center_px, up_px = leaf_markers(shape, dpmm, mlc, orientation, leaf_analysis_width_ratio)
+    if list(result.leaf_nums) != nums:
+        raise ValueError("the leaves in view of this shape / dpmm / mlc / orientation are not result.leaf_nums")
+    pos = ops._frames(result.position)
+    if pos.dtype != torch.float64 or result.status.shape != pos.shape or result.status.dtype != torch.int32:
+        raise TypeError("position float64 [N, leaves, cap] and status int32 of the same shape")
+    n, nl, cap = pos.shape
+    if nl != len(nums) or tuple(result.picket_count.shape) != (n,) or result.picket_count.dtype != torch.int32:
+        raise ValueError("position [N, leaves, cap] does not go with leaf_nums / picket_count int32 [N]")
+    dev = pos.device
+    pos, st, cnt = pos.contiguous(), result.status.contiguous(), result.picket_count.contiguous()
+    key = ("markers", tuple(nums), tuple(center_px), tuple(up_px), str(dev))
+    if key not in _PLAN_CACHE:
+        _PLAN_CACHE[key] = (torch.tensor(nums, dtype=torch.int32, device=dev),
+                            torch.tensor(center_px, dtype=torch.float64, device=dev),
+                            torch.tensor(up_px, dtype=torch.float64, device=dev))
+    d_num, d_center, d_up = _PLAN_CACHE[key]
+    fit = torch.empty((n, cap, 2), dtype=torch.float64, device=dev)
+    pst = torch.empty((n, cap), dtype=torch.int32, device=dev)
+    err = torch.empty((n, nl, cap), dtype=torch.float64, device=dev)
+    ok = torch.empty((n, nl, cap), dtype=torch.uint8, device=dev)
+    summary = torch.empty((n, len(PF_SUMMARY_FIELDS)), dtype=torch.float64, device=dev)
+    lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
+    check(lib.pl_pf_errors(pos.data_ptr(), st.data_ptr(), cnt.data_ptr(), n, nl, cap, d_num.data_ptr(), d_center.data_ptr(),
+                           d_up.data_ptr(), float(dpmm), tolerance,
+                           float("nan") if action_tolerance is None else float(action_tolerance), fit.data_ptr(), pst.data_ptr(),
+                           err.data_ptr(), ok.data_ptr(), summary.data_ptr(), stream), "pl_pf_errors")
+    return PFErrorsBatch(fit, pst, err, ok, summary)
