@@ -953,6 +953,39 @@ int pl_peak_ips_rows(const double* d_x, int64_t n, int len, const int32_t* d_cou
                      const int32_t* d_left_base, const int32_t* d_right_base, const double* d_props, int cap,
                      const double* d_rel_height, int nq, double* d_out, void* stream);
 
+/* ---- Starshot over a stack of frames (starshot.analyze_batch(analyzers=False), starshot.wobble_batch) ------------------------
+ * pl_starshot_roll: StarProfile.get_peaks' first step (pylinac/starshot.py:798-803) for n rings of `len` samples, d_x float64
+ * [n][len]: d_roll int32 [n] = np.where(values == values.min())[0][0], the FIRST minimum; d_out float64 [n][len] = np.roll(values,
+ * -d_roll).  Not in place. */
+int pl_starshot_roll(const double* d_x, int64_t n, int len, double* d_out, int32_t* d_roll, void* stream);
+/* pl_starshot_peaks: its last steps on the rolled, filtered and grounded rings d_x float64 [n][len]: pl_find_peaks with `params`
+ * except the height, which is d_threshold float64 [n] per ring (a value in [0, 1] is a ratio of the ring's range,
+ * pylinac/core/profile.py:2633-2635); outputs d_count .. d_status as pl_find_peaks, except that d_count is cap + 1 where the
+ * search ran out of room (status != 0).  Then the `peaks` list of the profile: d_peak_idx int32 [n][cap] = int(round(left_ips +
+ * (right_ips - left_ips) / 2)), half to even (fwhm != 0: find_fwxm_peaks, profile.py:2135-2176), or the peak's own index (fwhm
+ * == 0); d_points float64 [n][cap][2] = CircleProfile._map_peaks: (d_cos[j] * radius + cx, d_sin[j] * radius + cy) at j =
+ * (d_peak_idx + d_roll) % len, a multiply and an add; d_cos / d_sin float64 [len] = numpy's cos / sin of the ring's radians,
+ * d_geom float64 [n][3] = radius, cx, cy.  -1 / NaN beyond d_count. */
+int pl_starshot_peaks(const double* d_x, int64_t n, int len, const double* d_threshold, const int32_t* d_roll,
+                      const double* d_cos, const double* d_sin, const double* d_geom, int fwhm, const pl_peak_params* params,
+                      int cap, int32_t* d_count, int32_t* d_idx, int32_t* d_left_base, int32_t* d_right_base, double* d_props,
+                      int32_t* d_status, int32_t* d_peak_idx, double* d_points, void* stream);
+/* pl_starshot_wobble: what Starshot._accept and _find_wobble_minimize (pylinac/starshot.py:306-401) do behind the star profile,
+ * one lane per dataset: LineManager's lines (peaks[k] with peaks[k + n / 2]) and its test that every line passes within
+ * 10 * dpmm of the focus (strict >), the wobble circle by a replay of scipy.optimize.minimize(method="Nelder-Mead",
+ * options={"fatol": 0.001}) from (focus x, focus y, 0) in scipy's float64 operation order (same x, fun, nit, nfev), and the
+ * accept test (diameter_mm < max_wobble_diameter and dist(centre, focus) < 10 * dpmm) or not recursive.
+ *   d_points float64 [m][cap][2] = the peaks' (x, y) in the order of the profile's `peaks` list, d_count int32 [m] peaks per
+ *   dataset, d_focus float64 [m][2]; cap even, <= 64.
+ *   d_record float64 [m][9] = wobble centre x, y, radius px, radius_mm, diameter_mm, nit, nfev, n_lines, passed (1 / 0:
+ *   radius_mm * 2 < tolerance); NaN (n_lines and passed aside) when nothing was fitted;
+ *   d_lines float64 [m][cap / 2][4] = point1 x, y, point2 x, y, NaN beyond n_lines;
+ *   d_fit_status int32 [m]: 0 accepted; 1 fewer than 6 peaks or an odd number; 2 a line farther than 10 * dpmm from the focus;
+ *   3 fitted but not accepted (the numbers are written); 4 more peaks than cap. */
+int pl_starshot_wobble(const double* d_points, const int32_t* d_count, const double* d_focus, int64_t m, int cap, double dpmm,
+                       double max_wobble_diameter, double tolerance, int recursive, double* d_record, double* d_lines,
+                       int32_t* d_fit_status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,10 @@ SIGNATURES = {
     "pl_field_strips": ([_p, _i, _l, _i, _i, _p, _d, _d, _p, _p, _p, _p], C.c_int),
     "pl_field_windows": ([_p, _p, _l, _i, _p, _p, _d, _d, _i, _p, _p, _p, _p], C.c_int),
     "pl_peak_ips_rows": ([_p, _l, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p], C.c_int),
+    "pl_starshot_roll": ([_p, _l, _i, _p, _p, _p], C.c_int),
+    "pl_starshot_peaks": ([_p, _l, _i, _p, _p, _p, _p, _p, _i, C.POINTER(PeakParams), _i, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+                          C.c_int),
+    "pl_starshot_wobble": ([_p, _p, _p, _l, _i, _d, _d, _d, _i, _p, _p, _p, _p], C.c_int),
 }
 
 

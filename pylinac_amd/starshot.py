@@ -10,10 +10,15 @@ Dense work -- percentiles, grounding / inversion, axis maxima, the 20-radius nea
 and the peak / FWXM search -- runs in the kernels behind ``ArrayImage`` / ``CollapsedCircleProfile`` / ``FWXMProfile``.
 The wobble fit is the reference's own per-dataset optimiser (Nelder-Mead over <= a dozen lines, ``scipy.optimize``) on
 the host, and so is the parameter sweep that retries with other radii / peak heights.
+
+Over a stack, ``analyze_batch(..., analyzers=False)`` keeps the profile's tail and the wobble fit on the device too
+(``star_tail``, ``wobble_batch``: csrc/starshot.hip); the fit is a replay of scipy's Nelder-Mead in its own float64 operation
+order, so it stops where scipy stops.
 """
 from __future__ import annotations
 
 import copy
+import ctypes as C
 import math
 from dataclasses import dataclass, field
 from itertools import product
@@ -22,7 +27,7 @@ import numpy as np
 import torch
 from scipy import optimize
 
-from . import ops
+from . import _lib, ops
 from .array_utils import _Staged, _device
 from .geometry import Circle
 from .image import ArrayImage
@@ -273,6 +278,203 @@ class Starshot:
 
 
 # ---------------------------------------------------------------------------------------------------- the batched form
+WOBBLE_FIELDS = ("center_x", "center_y", "radius", "radius_mm", "diameter_mm", "nit", "nfev", "n_lines", "passed")
+WOBBLE_CAP = 64                       # peaks per dataset pl_starshot_wobble takes (32 lines)
+
+
+@dataclass
+class WobbleBatch:
+    """``wobble_batch``'s device-resident records, one row per dataset.  ``fit_status``: 0 accepted; 1 fewer than 6 peaks or
+    an odd number; 2 a line farther than ``10 * dpmm`` from the focus (``LineManager`` raises ValueError); 3 fitted but not
+    accepted (the numbers are written); 4 more peaks than the table holds."""
+
+    record: torch.Tensor               # float64 [M, 9]: WOBBLE_FIELDS (NaN when nothing was fitted)
+    lines: torch.Tensor                # float64 [M, cap / 2, 4]: point1 x, y, point2 x, y (NaN beyond n_lines)
+    fit_status: torch.Tensor           # int32 [M]
+
+    def __len__(self):
+        return self.fit_status.shape[0]
+
+
+def wobble_batch(points, counts, focus, dpmm: float, max_wobble_diameter: float = 2.0, tolerance: float = 1.0,
+                 recursive: bool = True) -> WobbleBatch:
+    """``Starshot._accept`` / ``_find_wobble_minimize`` for a table of datasets in one launch (``pl_starshot_wobble``):
+    ``points`` float64 [M, cap, 2] = the peaks' (x, y) in the order of ``StarProfile.peaks`` (cap even, at most 64),
+    ``counts`` int32 [M], ``focus`` float64 [M, 2].  The wobble circle is scipy's Nelder-Mead replayed in its own float64
+    operation order: centre, radius, ``nit`` and ``nfev`` are those of ``scipy.optimize.minimize``.  Nothing is synchronised."""
+    dev = points.device if isinstance(points, torch.Tensor) and points.is_cuda else _device()
+
+    def table(v, dtype):
+        t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))
+        return t.to(device=dev, dtype=dtype).contiguous()
+
+    pts, cnt, foc = table(points, torch.float64), table(counts, torch.int32), table(focus, torch.float64)
+    if pts.dim() != 3 or pts.shape[2] != 2:
+        raise ValueError("points must be [M, cap, 2]")
+    m, cap = int(pts.shape[0]), int(pts.shape[1])
+    if cap < 2 or cap > WOBBLE_CAP or cap % 2:
+        raise ValueError(f"cap must be an even number of peaks, at most {WOBBLE_CAP}")
+    if tuple(cnt.shape) != (m,) or tuple(foc.shape) != (m, 2):
+        raise ValueError("counts [M] and focus [M, 2] must go with points [M, cap, 2]")
+    if not float(dpmm) > 0:
+        raise ValueError("dpmm must be positive")
+    record = torch.empty((m, len(WOBBLE_FIELDS)), dtype=torch.float64, device=dev)
+    lines = torch.empty((m, cap // 2, 4), dtype=torch.float64, device=dev)
+    fit_status = torch.empty(m, dtype=torch.int32, device=dev)
+    if m == 0:
+        return WobbleBatch(record, lines, fit_status)
+    lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
+    _lib.check(lib.pl_starshot_wobble(pts.data_ptr(), cnt.data_ptr(), foc.data_ptr(), m, cap, float(dpmm),
+                                      float(max_wobble_diameter), float(tolerance), int(bool(recursive)), record.data_ptr(),
+                                      lines.data_ptr(), fit_status.data_ptr(), stream), "pl_starshot_wobble")
+    return WobbleBatch(record, lines, fit_status)
+
+
+def star_tail(values: torch.Tensor, thresholds, geometry, size: float, fwhm: bool = True, cap: int = WOBBLE_CAP):
+    """``StarProfile.get_peaks`` and ``CircleProfile._map_peaks`` for G rings of one sample count, with no per-ring launch:
+    ``values`` float64 [G, L] on the device (the collapsed ring gather), ``thresholds`` [G] the peak height of each ring
+    (``min_peak_height * local_max``; a value in [0, 1] is a ratio), ``geometry`` [G, 3] = the ring's radius, centre x, centre
+    y, ``size`` the ring's ``CircleProfile.size``.  Roll to the first minimum (``pl_starshot_roll``), the ``size=0.003``
+    Gaussian and ``ground`` of the batched library launches, then ``pl_starshot_peaks``.
+    -> (count int32 [G] -- ``cap + 1`` where the search ran out of room --, peak index int32 [G, cap], points float64
+    [G, cap, 2], processed values float64 [G, L], roll int32 [G]), all on the device."""
+    from .array_utils import resolve_filter_size
+
+    v = values.to(torch.float64).contiguous()
+    g, length = v.shape
+    dev = v.device
+    d_cos, d_sin, nsamp = ops._circle_tables(size, 0, True, dev)
+    if nsamp != length:
+        raise ValueError("values do not have the ring's number of samples")
+    pack = np.empty((4, g), dtype=np.float64)
+    pack[0] = np.asarray(thresholds, dtype=np.float64)
+    pack[1:].reshape(-1)[:] = np.ascontiguousarray(geometry, dtype=np.float64).reshape(-1)      # [G, 3] behind the heights
+    d_pack = torch.from_numpy(pack.reshape(-1)).to(dev)
+    d_thr, d_geom = d_pack[:g], d_pack[g:]
+    lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
+    rolled = torch.empty_like(v)
+    roll = torch.empty(g, dtype=torch.int32, device=dev)
+    _lib.check(lib.pl_starshot_roll(v.data_ptr(), g, length, rolled.data_ptr(), roll.data_ptr(), stream), "pl_starshot_roll")
+    smooth = ops.gaussian_filter1d(rolled, resolve_filter_size(length, 0.003))
+    grounded = ops.ground(smooth.view(g, 1, length), 0).view(g, length)
+    prm = ops.make_peak_params(length, threshold=0.5, peak_separation=0.02)      # the height is per ring: d_thr
+    count = torch.empty(g, dtype=torch.int32, device=dev)
+    ints = torch.empty((5, g, cap), dtype=torch.int32, device=dev)               # idx, bases, status (first row), peak idx
+    props = torch.empty((g, 6, cap), dtype=torch.float64, device=dev)
+    points = torch.empty((g, cap, 2), dtype=torch.float64, device=dev)
+    _lib.check(lib.pl_starshot_peaks(grounded.data_ptr(), g, length, d_thr.data_ptr(), roll.data_ptr(), d_cos.data_ptr(),
+                                     d_sin.data_ptr(), d_geom.data_ptr(), int(bool(fwhm)), C.byref(prm), cap, count.data_ptr(),
+                                     ints[0].data_ptr(), ints[1].data_ptr(), ints[2].data_ptr(), props.data_ptr(),
+                                     ints[3].data_ptr(), ints[4].data_ptr(), points.data_ptr(), stream), "pl_starshot_peaks")
+    return count, ints[4], points, grounded, roll
+
+
+def _angles_of(lines: np.ndarray) -> np.ndarray:
+    """``calculate_angles`` (starshot.py:817-834) over a NaN-padded line table [..., 4] in one vectorised call."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        m = (lines[..., 1] - lines[..., 3]) / (lines[..., 0] - lines[..., 2])
+        phi = np.degrees(np.arctan(m)) - 90
+    return np.where(phi > 90, phi - 180, np.where(phi <= -90, phi + 180, phi))
+
+
+def _device_sweep(x, out: "StarshotBatch", shape, dpmm, radius, min_peak_height, max_wobble_diameter, tolerance, fwhm,
+                  recursive) -> None:
+    """``_get_reasonable_wobble`` (starshot.py:306-376) for the frames of ``analyze_batch`` without a per-frame launch or
+    object: every pass of the retry sweep is, per ring size, the ring gather, ``star_tail`` and ``pl_starshot_wobble``, and
+    ONE transfer of the pass's records; the host advances each pending frame's (radius, peak height) pair and regroups.  A frame
+    whose ring holds more peaks than the table (fit_status 4) is finished by the class path for that pass."""
+    n = len(out.status)
+    status, local_max = out.status, out.local_max
+    half = WOBBLE_CAP // 2
+    out.analyzers = []
+    out.lines = np.full((n, half, 4), np.nan)
+    out.nit, out.nfev = np.full(n, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32)
+    state = {i: [Point(x=out.start_point[i, 0], y=out.start_point[i, 1]), radius, min_peak_height,
+                 _retry_sweep(radius, min_peak_height)] for i in range(n) if not status[i]}
+    width = len(WOBBLE_FIELDS) + half * 4 + 1
+
+    def accepted(i, rec, lines, rad, mph):
+        out.wobble_center[i] = rec[0:2]
+        out.wobble_radius[i], out.wobble_radius_mm[i], out.wobble_diameter_mm[i] = rec[2], rec[3], rec[4]
+        out.nit[i], out.nfev[i], out.n_lines[i], out.passed[i] = rec[5], rec[6], rec[7], bool(rec[8])
+        out.lines[i] = lines
+        out.radius[i], out.min_peak_height[i] = rad, mph
+
+    def class_path(i, ring, values, focus, rad, mph) -> bool:
+        """the default path's body for one frame and one pass; True = settled (accepted, or status 2)"""
+        a = object.__new__(Starshot)
+        a.image, a.wobble, a.tolerance = _FrameMeta(shape, dpmm), Wobble(), tolerance
+        try:
+            ring.values = values
+            ring.get_peaks(mph * local_max[i], fwhm=fwhm)
+            a.circle_profile = ring
+            if not a._accept(focus, recursive, max_wobble_diameter):
+                return False
+        except ValueError:
+            return False
+        except RuntimeError:
+            status[i] = 2
+            return True
+        table = np.full((half, 4), np.nan)
+        for k, ln in enumerate(a.lines.lines[:half]):
+            table[k] = (ln.point1.x, ln.point1.y, ln.point2.x, ln.point2.y)
+        accepted(i, (a.wobble.center.x, a.wobble.center.y, a.wobble.radius, a.wobble.radius_mm, a.wobble.diameter_mm, -1, -1,
+                     len(a.lines), a.passed), table, rad, mph)
+        return True
+
+    pending = list(state)
+    while pending:
+        rings, again = {}, []
+        for i in pending:
+            focus, rad, mph, _ = state[i]
+            try:
+                ring = StarProfile._ring(shape, focus, rad)
+            except ValueError:
+                again.append(i)
+                continue
+            rings.setdefault(float(ring.size), []).append((i, ring))
+        tails, order, kept = [], [], {}
+        for size, members in rings.items():
+            idx = np.array([i for i, _ in members], dtype=np.int64)
+            radii = np.stack([ring._radii for _, ring in members])
+            geom = np.array([[ring.radius, ring.center.x, ring.center.y] for _, ring in members], dtype=np.float64)
+            vals = ops.circle_profile(x, geom[:, 1].copy(), geom[:, 2].copy(), radii, size, 0, True, 20.0, combine=(idx, n, 0))
+            thr = np.array([state[i][2] * local_max[i] for i in idx], dtype=np.float64)
+            count, _, points, _, _ = star_tail(vals, thr, geom, size, fwhm, cap=WOBBLE_CAP)
+            tails.append((count, points, geom[:, 1:]))
+            for j, (i, ring) in enumerate(members):
+                order.append(i)
+                kept[i] = (ring, vals, j)
+        if tails:                                     # ONE fit launch for the pass's frames of every ring size, one transfer
+            fit = wobble_batch(torch.cat([t[1] for t in tails]), torch.cat([t[0] for t in tails]),
+                               np.concatenate([t[2] for t in tails]), dpmm, max_wobble_diameter, tolerance, recursive)
+            table = torch.cat([fit.record, fit.lines.view(len(order), half * 4),
+                               fit.fit_status.to(torch.float64).unsqueeze(1)], 1).cpu().numpy()
+        else:
+            table = np.empty((0, width))
+        for row, i in zip(table, order):
+            focus, rad, mph, _ = state[i]
+            fit_status = int(row[-1])
+            if fit_status == 0:
+                accepted(i, row[:len(WOBBLE_FIELDS)], row[len(WOBBLE_FIELDS):-1].reshape(half, 4), rad, mph)
+            elif fit_status == 4:
+                ring, vals, j = kept[i]
+                if not class_path(i, ring, vals[j].cpu().numpy(), focus, rad, mph):
+                    again.append(i)
+            elif fit_status == 1 and not recursive:
+                status[i] = 2                                   # "unable to properly detect the radiation lines"
+            else:
+                again.append(i)
+        pending = []
+        for i in sorted(again):
+            try:
+                state[i][1], state[i][2] = next(state[i][3])
+                pending.append(i)
+            except StopIteration:
+                status[i] = 1
+    out.angles = _angles_of(out.lines)
+
+
 @dataclass
 class StarshotBatch:
     """``analyze_batch``'s records, one row per frame.  ``status``: 0 measured; 1 the (radius, peak height) sweep ran out
@@ -293,6 +495,11 @@ class StarshotBatch:
     radius: np.ndarray                 # float64 [N]: the (radius, min_peak_height) pair that was accepted
     min_peak_height: np.ndarray
     analyzers: list = field(default_factory=list)   # per frame: a ``Starshot`` with circle_profile / lines / wobble / angles
+    # analyze_batch(analyzers=False) only (None otherwise): the arrays that stand in for the per-frame objects
+    lines: np.ndarray | None = None    # float64 [N, 32, 4]: point1 x, y, point2 x, y of every radiation line, NaN-padded
+    angles: np.ndarray | None = None   # float64 [N, 32]: calculate_angles of the lines (degrees), NaN-padded
+    nit: np.ndarray | None = None      # int32 [N]: iterations and evaluations of the accepted wobble fit (-1: no fit, or a
+    nfev: np.ndarray | None = None     # frame finished on the per-frame path)
 
     def __len__(self):
         return len(self.status)
@@ -307,9 +514,13 @@ class _FrameMeta:
 
 def analyze_batch(frames, dpi: float | None = None, sid: float | None = None, radius: float = 0.85,
                   min_peak_height: float = 0.25, max_wobble_diameter: float = 2.0, tolerance: float = 1.0,
-                  fwhm: bool = True, recursive: bool = True, invert: bool = False) -> StarshotBatch:
+                  fwhm: bool = True, recursive: bool = True, invert: bool = False, analyzers: bool = True) -> StarshotBatch:
     """``Starshot(frame, dpi=, sid=).analyze(...)`` (pylinac/starshot.py:229-401) for every frame of a uint16 / int16 stack
     [N, H, W] resident in HBM, with the per-frame error cases as status codes.
+
+    ``analyzers=False`` keeps everything behind the ring gather on the device as well (``_device_sweep``): the result holds
+    no per-frame ``Starshot`` objects (``analyzers`` is empty) but the ``lines`` / ``angles`` / ``nit`` / ``nfev`` arrays; every
+    other field equals the default path's.  What follows describes the default, ``analyzers=True``.
 
     Everything that touches pixels runs over the whole stack: the [4, 50, 96] percentiles of the inversion check (exact
     histogram), inversion of the frames that need it, grounding, the axis maxima of the central third and their FW80M
@@ -386,6 +597,9 @@ def analyze_batch(frames, dpi: float | None = None, sid: float | None = None, ra
                         local_max=local_max, inverted=inverted, radius=np.full(n, np.nan),
                         min_peak_height=np.full(n, np.nan), analyzers=[None] * n)
     shape = (h, w)
+    if not analyzers:
+        _device_sweep(x, out, shape, dpmm, radius, min_peak_height, max_wobble_diameter, tolerance, fwhm, recursive)
+        return out
     state = {}
     for i in range(n):
         if status[i]:
