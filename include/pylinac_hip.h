@@ -509,6 +509,23 @@ int64_t pl_xim_work_bytes(int width, int height);
 int pl_xim_decode(const unsigned char* d_lookup, int64_t lookup_bytes, const unsigned char* d_stream,
                   int64_t stream_bytes, int width, int height, int bytes_per_pixel, void* d_out,
                   unsigned char* d_work, void* stream);
+/* The same decoding (pylinac/core/image.py:1180-1296) for a STACK of n compressed images that share one (width, height,
+ * bytes_per_pixel) and lie anywhere inside one device buffer (whole .xim files copied as they are): image i has its lookup
+ * table at byte d_lut_off[i] (d_lut_len[i] bytes) and its compressed pixel buffer at byte d_buf_off[i] (d_buf_len[i] bytes),
+ * int64 [n] device arrays, any alignment.  The number of launches does not depend on n and nothing is read back.
+ *   out_kind 0: d_out = the container dtype [n][height][width], bit-identical with pl_xim_decode;
+ *            1: uint16, `array.astype(np.uint16)` (wrap-around);  2: float64, `array.astype(np.float64)`;
+ *   d_status int32 [n] (zeroed here), per image: bit 0 a size code 3 occurred (the reference raises KeyError(3); nothing else
+ *   is reported for that image), bit 1 the lookup table or the pixel buffer is shorter than width * height implies or does
+ *   not lie inside [0, buffer_bytes) (such an image is never read and its frame is not finished), bit 2 (out_kind 1) a
+ *   pixel lay outside 0 .. 65535.  A flagged image does not disturb the others.
+ *   d_work: pl_xim_batch_work_bytes() bytes on a 16-byte boundary (-1 for arguments pl_xim_decode_batch refuses).
+ * height >= 2, 1 <= n <= 65535 (else invalid argument); bytes_per_pixel 1 / 2 / 4 / 8 (else unsupported). */
+int64_t pl_xim_batch_work_bytes(int n, int width, int height, int bytes_per_pixel, int out_kind);
+int pl_xim_decode_batch(const unsigned char* d_buffer, int64_t buffer_bytes, const int64_t* d_lut_off,
+                        const int64_t* d_lut_len, const int64_t* d_buf_off, const int64_t* d_buf_len, int n, int width,
+                        int height, int bytes_per_pixel, int out_kind, void* d_out, int32_t* d_status,
+                        unsigned char* d_work, void* stream);
 
 /* ---- f1 ("next" row), the DICOM half: native (uncompressed) Pixel Data -> typed frames -------------------------
  * Replaces `self.metadata.pixel_array` [+ `.astype(dtype)`] [+ `pixels.apply_rescale`] of DicomImage.__init__

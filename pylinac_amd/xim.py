@@ -3,11 +3,19 @@
 ``decode_xim_pixels`` is the kernel-level entry (``pl_xim_decode``); ``XIM`` mirrors ``pylinac.core.image.XIM``'s
 reader (pylinac/core/image.py:1105-1296): same attributes (``img_width_px``, ``img_height_px``, ``bytes_per_pixel``,
 ``compression``, ``lookup_table``, ``histogram``, ``properties``, ``dpmm``) and the pixel ``array`` as a device
-tensor.  The header / property parsing is host I/O like the reference's ``decode_binary`` calls.
+tensor.  The header / property parsing is host I/O like the reference's ``decode_binary`` calls (``parse_xim``, shared
+by ``XIM``, ``XIM.from_bytes`` and the loader).
+
+``load_frames`` is the batched form the reference does not have: a session's compressed files -> one pinned buffer -> one
+copy -> ONE ``pl_xim_decode_batch`` call (``decode_xim_batch``, the kernel-level entry of the stack) -> ``XIMStack`` with
+``[N, H, W]`` frames in the container dtype, uint16 or float64 and a per-file status, nothing read back unless ``check``.
 """
 from __future__ import annotations
 
+import os
 import struct
+from dataclasses import dataclass
+from pathlib import Path
 
 import numpy as np
 import torch
@@ -44,8 +52,27 @@ def decode_xim_pixels(lookup_table_bytes, stream, width: int, height: int, bytes
     if status & 1:
         raise KeyError(3)          # the reference's LOOKUP_CONVERSION has no entry for size code 3
     if status & 2:
-        raise ValueError("XIM pixel buffer is shorter than its lookup table implies")
+        raise ValueError(_SHORT)
     return out
+
+
+class _Cursor:
+    """``read`` / ``skip`` / ``tell`` over a bytes-like object without copying it (``read`` returns a memoryview)."""
+
+    def __init__(self, data):
+        self.buf = memoryview(data).cast("B")
+        self.pos = 0
+
+    def read(self, n: int):
+        out = self.buf[self.pos:self.pos + n]
+        self.pos += n
+        return out
+
+    def skip(self, n: int):
+        self.pos += n
+
+    def tell(self) -> int:
+        return self.pos
 
 
 def _read(f, fmt: str, n: int = 1):
@@ -57,55 +84,102 @@ def _read_str(f, n: int) -> str:
     return "".join(chr(b) for b in f.read(n) if b != 0)
 
 
+def _source_bytes(source) -> bytes:
+    """A path, a bytes-like object or a binary file object -> the file's bytes (what ``dicom.load_frames`` accepts)."""
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        return bytes(source)
+    if isinstance(source, np.ndarray):
+        return source.tobytes()
+    if isinstance(source, (str, Path)):
+        with open(source, "rb") as f:
+            return f.read()
+    if hasattr(source, "seek"):
+        source.seek(0)
+    return source.read()
+
+
+def parse_xim(data, target, on_pixels=None):
+    """The reader of pylinac/core/image.py:1123-1178 over a bytes-like object: header fields, ``lookup_table``, ``histogram``
+    and ``properties`` are set on ``target`` -> ((lookup-table offset, length) or None for an uncompressed file, (pixel-buffer
+    offset, length)), byte positions inside ``data``.  ``on_pixels(lut_span, buf_span)`` is called where the reference reads
+    the pixels, before the histogram and the properties."""
+    xim = _Cursor(data)
+    target.format_id = _read_str(xim, 8)
+    target.format_version = _read(xim, "i")
+    target.img_width_px = _read(xim, "i")
+    target.img_height_px = _read(xim, "i")
+    target.bits_per_pixel = _read(xim, "i")
+    target.bytes_per_pixel = _read(xim, "i")
+    target.compression = _read(xim, "i")
+    if not target.compression:
+        pixel_buffer_size = _read(xim, "i")
+        lut_span, buf_span = None, (xim.tell(), pixel_buffer_size)
+        xim.skip(pixel_buffer_size)
+        if on_pixels is not None:
+            on_pixels(lut_span, buf_span)
+    else:
+        lookup_table_size = _read(xim, "i")
+        lut_span = (xim.tell(), lookup_table_size)
+        target.lookup_table = np.frombuffer(xim.read(lookup_table_size), dtype=np.uint8)
+        comp_pixel_buffer_size = _read(xim, "i")
+        buf_span = (xim.tell(), comp_pixel_buffer_size)
+        xim.skip(comp_pixel_buffer_size)
+        if on_pixels is not None:
+            on_pixels(lut_span, buf_span)
+        _read(xim, "i")                                           # uncompressed size (unused by the reference)
+    target.num_hist_bins = _read(xim, "i")
+    target.histogram = _read(xim, "i", target.num_hist_bins) if target.num_hist_bins else np.array([], dtype=int)
+    target.num_properties = _read(xim, "i")
+    target.properties = {}
+    for _ in range(target.num_properties):
+        name = _read_str(xim, _read(xim, "i"))
+        tipe = _read(xim, "i")
+        if tipe == XIM_PROP_INT:
+            value = _read(xim, "i")
+        elif tipe == XIM_PROP_DOUBLE:
+            value = _read(xim, "d")
+        elif tipe == XIM_PROP_STRING:
+            value = _read_str(xim, _read(xim, "i"))
+        elif tipe == XIM_PROP_DOUBLE_ARRAY:
+            value = _read(xim, "d", int(_read(xim, "i") // 8))
+        elif tipe == XIM_PROP_INT_ARRAY:
+            value = _read(xim, "i", int(_read(xim, "i") // 4))
+        else:
+            raise ValueError(f"unknown XIM property type {tipe}")
+        target.properties[name] = value
+    return lut_span, buf_span
+
+
 class XIM:
     """pylinac/core/image.py:1105-1178 (reader) with the pixel decoding on the GPU."""
 
     def __init__(self, file_path, read_pixels: bool = True, device=None):
         self.path = file_path
         with open(file_path, "rb") as xim:
-            self.format_id = _read_str(xim, 8)
-            self.format_version = _read(xim, "i")
-            self.img_width_px = _read(xim, "i")
-            self.img_height_px = _read(xim, "i")
-            self.bits_per_pixel = _read(xim, "i")
-            self.bytes_per_pixel = _read(xim, "i")
-            self.compression = _read(xim, "i")
-            if not self.compression:
-                pixel_buffer_size = _read(xim, "i")
-                raw = np.frombuffer(xim.read(pixel_buffer_size), dtype=np.uint8)
-                if read_pixels:
-                    dt = {1: np.int8, 2: np.int16, 4: np.int32, 8: np.int64}[self.bytes_per_pixel]
-                    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-                    self.array = torch.from_numpy(raw.view(dt).reshape(self.img_height_px, self.img_width_px).copy()).to(dev)
+            data = xim.read()
+        self._load(data, read_pixels, device)
+
+    @classmethod
+    def from_bytes(cls, data, read_pixels: bool = True, device=None) -> "XIM":
+        """The same reader over the bytes of a file (``path`` is None)."""
+        self = cls.__new__(cls)
+        self.path = None
+        self._load(bytes(data), read_pixels, device)
+        return self
+
+    def _load(self, data: bytes, read_pixels: bool, device):
+        def pixels(lut_span, buf_span):
+            raw = np.frombuffer(data, dtype=np.uint8, count=max(0, min(buf_span[1], len(data) - buf_span[0])),
+                                offset=buf_span[0])
+            if lut_span is None:
+                dt = {1: np.int8, 2: np.int16, 4: np.int32, 8: np.int64}[self.bytes_per_pixel]
+                dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+                self.array = torch.from_numpy(raw.view(dt).reshape(self.img_height_px, self.img_width_px).copy()).to(dev)
             else:
-                lookup_table_size = _read(xim, "i")
-                self.lookup_table = np.frombuffer(xim.read(lookup_table_size), dtype=np.uint8)
-                comp_pixel_buffer_size = _read(xim, "i")
-                stream = np.frombuffer(xim.read(comp_pixel_buffer_size), dtype=np.uint8)
-                if read_pixels:
-                    self.array = decode_xim_pixels(self.lookup_table, stream, self.img_width_px, self.img_height_px,
-                                                   self.bytes_per_pixel, device=device)
-                _read(xim, "i")                                           # uncompressed size (unused by the reference)
-            self.num_hist_bins = _read(xim, "i")
-            self.histogram = _read(xim, "i", self.num_hist_bins) if self.num_hist_bins else np.array([], dtype=int)
-            self.num_properties = _read(xim, "i")
-            self.properties = {}
-            for _ in range(self.num_properties):
-                name = _read_str(xim, _read(xim, "i"))
-                tipe = _read(xim, "i")
-                if tipe == XIM_PROP_INT:
-                    value = _read(xim, "i")
-                elif tipe == XIM_PROP_DOUBLE:
-                    value = _read(xim, "d")
-                elif tipe == XIM_PROP_STRING:
-                    value = _read_str(xim, _read(xim, "i"))
-                elif tipe == XIM_PROP_DOUBLE_ARRAY:
-                    value = _read(xim, "d", int(_read(xim, "i") // 8))
-                elif tipe == XIM_PROP_INT_ARRAY:
-                    value = _read(xim, "i", int(_read(xim, "i") // 4))
-                else:
-                    raise ValueError(f"unknown XIM property type {tipe}")
-                self.properties[name] = value
+                self.array = decode_xim_pixels(self.lookup_table, raw, self.img_width_px, self.img_height_px,
+                                               self.bytes_per_pixel, device=device)
+
+        self._spans = parse_xim(data, self, pixels if read_pixels else None)
 
     @property
     def dpmm(self) -> float:
@@ -113,3 +187,149 @@ class XIM:
         if self.properties["PixelWidth"] != self.properties["PixelHeight"]:
             raise ValueError("The XIM image does not have the same pixel height and width")
         return 1 / (10 * self.properties["PixelHeight"])
+
+
+_OUT_KINDS = {None: 0, np.dtype(np.uint16): 1, np.dtype(np.float64): 2}
+_SHORT = "XIM pixel buffer is shorter than its lookup table implies"
+
+
+def _out_kind(dtype) -> int:
+    try:
+        return _OUT_KINDS[None if dtype is None else np.dtype(dtype)]
+    except (KeyError, TypeError):
+        raise TypeError(f"dtype {dtype!r}: None (the container dtype), np.uint16 or np.float64") from None
+
+
+def decode_xim_batch(buffer, lut_off, lut_len, buf_off, buf_len, width: int, height: int, bytes_per_pixel: int, dtype=None,
+                     device=None):
+    """``pl_xim_decode_batch``, the stack counterpart of ``decode_xim_pixels``: N compressed images of one (width, height,
+    bytes_per_pixel) anywhere inside ``buffer`` (uint8 array / tensor; a device tensor is used in place); image i has its
+    lookup table at byte ``lut_off[i]`` (``lut_len[i]`` bytes) and its pixel buffer at ``buf_off[i]`` (``buf_len[i]``
+    bytes).  -> (frames [N, height, width] in the container dtype, ``np.uint16`` or ``np.float64``; status int32 [N]), both
+    on the device, nothing read back.  status bits: 1 a size code 3 (the reference's ``KeyError(3)``), 2 a lookup table or
+    pixel buffer shorter than the shape implies or outside the buffer, 4 (uint16) a pixel outside 0 .. 65535."""
+    kind = _out_kind(dtype)
+    if bytes_per_pixel not in _DTYPES:
+        raise ValueError("The XIM image has an unsupported bytes per pixel value. "
+                         "Raise a ticket on the pylinac Github with this file.")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(buffer, torch.Tensor):
+        host = np.ascontiguousarray(buffer, dtype=np.uint8)
+        buffer = torch.from_numpy(host if host.flags.writeable else host.copy())
+    buf = buffer.to(device=dev, dtype=torch.uint8).contiguous()
+
+    def index(a):
+        if isinstance(a, torch.Tensor):
+            return a.to(device=dev, dtype=torch.int64).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+
+    spans = [index(a) for a in (lut_off, lut_len, buf_off, buf_len)]
+    n = int(spans[0].numel())
+    if any(int(s.numel()) != n or s.dim() != 1 for s in spans):
+        raise ValueError("decode_xim_batch: the four offset / length arrays must be 1-D and of one size")
+    lib = _lib.load()
+    nwork = int(lib.pl_xim_batch_work_bytes(n, width, height, bytes_per_pixel, kind))
+    work = torch.empty(max(nwork, 16), dtype=torch.uint8, device=dev)
+    odt = (_DTYPES[bytes_per_pixel], torch.uint16, torch.float64)[kind]
+    frames = torch.empty((n, height, width), dtype=odt, device=dev)
+    status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    check(lib.pl_xim_decode_batch(buf.data_ptr(), buf.numel(), *(s.data_ptr() for s in spans), n, width, height,
+                                  bytes_per_pixel, kind, frames.data_ptr(), status.data_ptr(), work.data_ptr(),
+                                  torch.cuda.current_stream(dev).cuda_stream), "pl_xim_decode_batch")
+    return frames, status[:n]
+
+
+@dataclass
+class XIMStack:
+    """What ``load_frames`` returns: ``frames`` [N, H, W] and ``status`` int32 [N] on the device, ``images`` the N files as
+    ``XIM(path, read_pixels=False)`` has them (header fields, ``lookup_table``, ``histogram``, ``properties``, ``dpmm``)."""
+    frames: torch.Tensor
+    status: torch.Tensor
+    images: list
+
+    @property
+    def dpmm(self) -> float:
+        """The files' common ``dpmm``; ``ValueError`` when they disagree."""
+        values = [x.dpmm for x in self.images]
+        if any(v != values[0] for v in values[1:]):
+            raise ValueError("the XIM files of the stack differ in dpmm")
+        return values[0]
+
+
+def _stage(sources, device=None):
+    """The host half of ``load_frames``: every file parsed, laid at a 4-byte boundary of one pinned buffer, ONE copy of that
+    buffer queued -> (images, device buffer, int64 [4, N] device array of lookup offset / length and pixel-buffer offset /
+    length inside it)."""
+    sources = list(sources)
+    if not sources:
+        raise ValueError("load_frames: no files")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    # sizes first, so that the files are read straight into the pinned buffer and parsed where they lie
+    held = [s if isinstance(s, (str, Path)) else _source_bytes(s) for s in sources]
+    sizes = [os.path.getsize(s) if isinstance(s, (str, Path)) else len(s) for s in held]
+    starts, pos = [], 0
+    for size in sizes:
+        starts.append(pos)
+        pos += (size + 3) & ~3
+    dbuf = torch.empty(pos, dtype=torch.uint8, device=dev)
+    host = torch.empty(pos, dtype=torch.uint8, pin_memory=dbuf.device.type == "cuda")
+    hv = host.numpy()
+    images = []
+    for s, st, size in zip(held, starts, sizes):
+        if isinstance(s, (str, Path)):
+            with open(s, "rb", buffering=0) as f:
+                got = f.readinto(memoryview(hv[st:st + size]))
+            if got != size:
+                raise OSError(f"{s}: read {got} of {size} bytes")
+        else:
+            hv[st:st + size] = np.frombuffer(s, dtype=np.uint8)
+        hv[st + size:st + ((size + 3) & ~3)] = 0
+        x = XIM.__new__(XIM)
+        x.path = s if isinstance(s, (str, Path)) else None
+        x._spans = parse_xim(hv[st:st + size], x)
+        if x.compression:
+            x.lookup_table = x.lookup_table.copy()           # (not a view of the pinned buffer, which is handed back)
+        images.append(x)
+    first = images[0]
+    for k, x in enumerate(images):
+        if not x.compression:
+            raise ValueError(f"load_frames: {_name(images, k)} is not compressed; read it with XIM(path)")
+        if x.bytes_per_pixel not in _DTYPES:
+            raise ValueError("The XIM image has an unsupported bytes per pixel value. "
+                             "Raise a ticket on the pylinac Github with this file.")
+        shape = (x.img_width_px, x.img_height_px, x.bytes_per_pixel)
+        if shape != (first.img_width_px, first.img_height_px, first.bytes_per_pixel):
+            raise ValueError(f"load_frames: {_name(images, k)} differs from file 0 in width, height or bytes per pixel: "
+                             f"{shape} against {(first.img_width_px, first.img_height_px, first.bytes_per_pixel)}")
+    dbuf.copy_(host, non_blocking=True)
+    spans = np.array([[st + x._spans[0][0], x._spans[0][1], st + x._spans[1][0], x._spans[1][1]]
+                      for st, x in zip(starts, images)], dtype=np.int64).T
+    return images, dbuf, torch.from_numpy(np.ascontiguousarray(spans)).to(dev)
+
+
+def _name(images, k: int) -> str:
+    return f"file {k}" + (f" ({images[k].path})" if images[k].path is not None else "")
+
+
+def load_frames(sources, dtype=None, device=None, check: bool = True) -> XIMStack:
+    """The batched loader the reference does not have: compressed .xim files (paths, bytes or binary file objects) of ONE
+    width, height and bytes per pixel -> ``XIMStack``.  Every file is parsed on the host and laid at a 4-byte boundary of one
+    pinned buffer; one copy takes that buffer to the device, ONE ``pl_xim_decode_batch`` call decodes every image where it
+    lies and stores ``dtype`` (None: the container dtype, ``np.uint16`` or ``np.float64`` = ``array.astype(dtype)``).
+    ``check=True`` reads the status once and raises for the first flagged file what ``XIM(path)`` raises (``KeyError(3)``,
+    ``ValueError``), or a ``ValueError`` for a file that does not fit uint16; ``check=False`` transfers nothing back."""
+    _out_kind(dtype)                       # TypeError before any file is read
+    images, dbuf, spans = _stage(sources, device)
+    first = images[0]
+    frames, status = decode_xim_batch(dbuf, spans[0], spans[1], spans[2], spans[3], first.img_width_px, first.img_height_px,
+                                      first.bytes_per_pixel, dtype=dtype, device=dbuf.device)
+    stack = XIMStack(frames=frames, status=status, images=images)
+    if check:
+        flags = status.cpu().numpy()
+        for k in np.flatnonzero(flags):
+            if flags[k] & 1:
+                raise KeyError(3)      # the reference's LOOKUP_CONVERSION has no entry for size code 3
+            if flags[k] & 2:
+                raise ValueError(_SHORT)
+            raise ValueError(f"load_frames: {_name(images, int(k))} holds pixels outside 0 .. 65535 and does not fit uint16")
+    return stack
