@@ -546,6 +546,31 @@ int pl_dicom_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t*
                     int bits_allocated, int bits_stored, int pixel_representation, int big_endian, int unused_bits,
                     void* d_out, int out_dtype, int rescale, double slope, double intercept, int32_t* d_status,
                     void* stream);
+/* RLE Lossless Pixel Data (transfer syntax 1.2.840.10008.1.2.5; PS3.5 Annex G, section A.4.2) -> the native little-endian
+ * frame buffer pl_dicom_decode reads: pydicom 2.x pixel_data_handlers/rle_handler.py `_rle_decode_frame` /
+ * `_rle_decode_segment` for a batch of frames whose fragments lie anywhere inside one device buffer (whole Part-10 files
+ * copied as they are).  SamplesPerPixel 1: a frame has `segments` = BitsAllocated / 8 PackBits segments, the most
+ * significant byte plane first; segment s of frame f is the d_seg_len[f * segments + s] bytes at byte
+ * d_seg_off[f * segments + s] (int64 [n_frames][segments] device arrays, any alignment; the host reads them from the
+ * fragment's 64-byte header).  A control byte c < 128 copies the next c + 1 bytes (fewer when the segment ends first),
+ * c > 128 repeats the next byte 257 - c times (nothing when the segment has ended), c = 128 does nothing; the first
+ * rows * cols decoded bytes of segment s become byte (segments - 1 - s) of the samples of d_native
+ * [n_frames][rows * cols * segments], whatever follows them is dropped.  Three passes over chunks of PL_DICOM_RLE_CHUNK
+ * input bytes (a table of exits and counts per chunk and entry offset 0 .. 128, the chain over the chunks, the expansion):
+ * the number of launches does not depend on n_frames and nothing is read back.
+ *   max_segment_bytes: an upper bound of every d_seg_len (it sizes the tables and the grid);
+ *   d_status int32 [n_frames] (zeroed here), per frame: bit 0 a segment window does not lie inside [0, nbytes) or is longer
+ *   than max_segment_bytes (nothing of that frame is read or written), bit 1 a segment decoded to fewer than rows * cols
+ *   bytes (pydicom raises ValueError), bit 2 a segment decoded to more (pydicom warns of non-conformant padding; the frame
+ *   is complete).  A flagged frame does not disturb the others.
+ *   d_work: pl_dicom_rle_work_bytes() bytes on a 16-byte boundary (-1 for arguments pl_dicom_rle_decode refuses).
+ * segments 1 / 2 / 4 (else unsupported); 1 <= n_frames <= 65535, rows, cols >= 1, non-null pointers (else invalid
+ * argument): checked before any launch. */
+#define PL_DICOM_RLE_CHUNK 1024
+int64_t pl_dicom_rle_work_bytes(int64_t n_frames, int segments, int64_t max_segment_bytes);
+int pl_dicom_rle_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_seg_off, const int64_t* d_seg_len,
+                        int64_t n_frames, int segments, int64_t max_segment_bytes, int rows, int cols,
+                        unsigned char* d_native, int32_t* d_status, unsigned char* d_work, void* stream);
 
 /* ---- f2 ("next" row, first half): skimage.feature.canny as called at pylinac/planar_imaging.py:574-588 -------
  * float64 images, mask=None.  The caller composes: G = pl_gaussian2d_mode(mode 2) of the image and of an all-ones

@@ -211,3 +211,348 @@ extern "C" int pl_dicom_decode(const unsigned char* d_bytes, int64_t nbytes, con
 #undef DC_LAUNCH
   return pl_check_launch("pl_dicom_decode");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// RLE Lossless Pixel Data (transfer syntax 1.2.840.10008.1.2.5; PS3.5 Annex G and section A.4.2) -> the NATIVE frame buffer
+// pl_dicom_decode reads.  The arithmetic is pydicom 2.x's pixel_data_handlers/rle_handler.py: `_rle_decode_frame` takes
+// segment s of a frame (SamplesPerPixel 1: BitsAllocated / 8 segments, the MOST significant byte plane first) through
+// `_rle_decode_segment`, a PackBits walk: control byte c, then
+//   c < 128: the next c + 1 bytes are copied (fewer when the segment ends first);
+//   c > 128: the next byte is repeated 257 - c times (nothing when the segment has ended);
+//   c = 128: nothing;
+// until the segment's bytes are used up.  The first rows * cols decoded bytes are the plane; fewer is pydicom's ValueError
+// ("The amount of decoded RLE segment data doesn't match the expected amount"), more its "non-conformant padding" warning.
+//
+// A walk is a chain of control bytes -- up to a million dependent steps for a 1024 x 1024 plane -- and no lane walks one.
+// Every segment is cut into chunks of kRleChunk INPUT bytes.  A control byte before a chunk starts a run that ends at most
+// 128 bytes into it (c = 127 at the chunk's last byte: 1 + 128 bytes), so the chunk's first true control byte lies at an
+// ENTRY OFFSET 0 .. 128 -- 129 cases, whatever came before:
+//   pass 1 (chunks x segments x frames): next[i] / out[i] for every position of the chunk as if it were a control byte, then
+//          pointer doubling in LDS (at most kRleRounds rounds): for each entry offset, where the walk leaves the chunk (an entry
+//          offset of the next one) and how many bytes it produces inside it -> a [chunks][129] table of (count << 8 | exit);
+//   pass 2 (segments x frames): the chain e_0 = 0, e_{j+1} = exit[j][e_j], off_{j+1} = off_j + count[j][e_j] over the table,
+//          staged into LDS a batch of rows at a time; the final offset gives the status bits (short / extra);
+//   pass 3 (chunks x segments x frames): the chunk knows its entry and its output offset: the same next[] at up to ten doubling
+//          levels marks the positions the walk visits, a scan over the marked controls gives every run its output offset,
+//          and groups of 16 lanes expand the runs into byte (bytes_per_sample - 1 - s) of the little-endian samples.
+// Every byte a lane reads lies inside its segment's [offset, offset + length) window, which every pass checks against the
+// buffer first: a frame with a window outside it (or longer than max_segment_bytes, which sizes the tables) is flagged with
+// status bit 0 and touched by no pass.
+namespace {
+
+constexpr int kRleChunk = PL_DICOM_RLE_CHUNK;              // input bytes per chunk
+constexpr int kRleThreads = 256;
+constexpr int kRlePer = kRleChunk / kRleThreads;           // positions per lane
+constexpr int kRleEntries = 129;                           // entry offsets 0 .. 128
+constexpr int kRleRounds = 10;                             // 2^kRleRounds >= kRleChunk: a walk makes at most one step per byte
+constexpr int kRleBatch = 64;                              // table rows pass 2 stages at a time (64 * 129 * 4 = 33 KB of LDS)
+constexpr int kRleGroup = 16;                              // lanes that expand one run
+static_assert(kRleChunk >= 129 && kRleChunk % kRleThreads == 0 && (1 << kRleRounds) >= kRleChunk, "chunk size");
+static_assert((int64_t)kRleChunk * 64 < (1 << 24), "a chunk's output count shares a word with its exit offset");
+static_assert(kRleThreads >= kRleEntries, "one lane per entry offset");
+
+struct RleWindow {
+  const unsigned char* seg;                                // this workgroup's segment
+  int64_t len;
+  bool ok;                                                 // every segment window of the FRAME lies inside the buffer
+};
+
+__device__ __forceinline__ RleWindow rle_window(const unsigned char* __restrict__ bytes, int64_t nbytes,
+                                                const int64_t* __restrict__ seg_off, const int64_t* __restrict__ seg_len,
+                                                int64_t frame, int segments, int seg, int64_t max_segment_bytes) {
+  RleWindow w;
+  w.ok = true;
+  for (int s = 0; s < segments; ++s) {
+    const int64_t o = seg_off[frame * segments + s], l = seg_len[frame * segments + s];
+    // (differences of lengths, never sums of an offset and a length: nothing here can overflow)
+    w.ok = w.ok && o >= 0 && l >= 0 && o <= nbytes && l <= nbytes - o && l <= max_segment_bytes;
+  }
+  w.seg = bytes + (w.ok ? seg_off[frame * segments + seg] : 0);
+  w.len = w.ok ? seg_len[frame * segments + seg] : 0;
+  return w;
+}
+
+// position p of a chunk read as a control byte c; `after` = the segment's bytes that follow p (<= 0: p is its last byte)
+// -> the position of the next control byte and the bytes this one produces
+__device__ __forceinline__ void rle_step(unsigned c, int p, int64_t after, int& next, int& out) {
+  if (c < 128u) {
+    const int n = (int)c + 1;
+    next = p + 1 + n;
+    out = after >= n ? n : (after > 0 ? (int)after : 0);
+  } else if (c > 128u) {
+    next = p + 2;
+    out = after > 0 ? 257 - (int)c : 0;
+  } else {
+    next = p + 1;
+    out = 0;
+  }
+}
+
+// exclusive prefix of `mine` over the kRleThreads lanes of a workgroup (every lane calls it)
+template <typename U>
+__device__ __forceinline__ U rle_block_exclusive(U mine, U* s_w) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  U inc = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const U v = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += v;
+  }
+  if (lane == 63) s_w[wv] = inc;
+  __syncthreads();
+  U off = inc - mine;
+  for (int q = 0; q < wv; ++q) off += s_w[q];
+  return off;
+}
+
+// pass 1
+__global__ void __launch_bounds__(kRleThreads)
+rle_table_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const int64_t* __restrict__ seg_off,
+                 const int64_t* __restrict__ seg_len, int segments, int64_t max_segment_bytes, int64_t n_chunks,
+                 unsigned* __restrict__ table, int32_t* __restrict__ status) {
+  // nodes 0 .. kRleChunk + 128: a node at or beyond the chunk's bytes is an exit (it points at itself and produces nothing)
+  __shared__ unsigned short s_next[kRleChunk + kRleEntries];
+  __shared__ unsigned s_out[kRleChunk + kRleEntries];
+  const int64_t frame = blockIdx.z, j = blockIdx.x;
+  const int seg = blockIdx.y;
+  const RleWindow win = rle_window(bytes, nbytes, seg_off, seg_len, frame, segments, seg, max_segment_bytes);
+  if (!win.ok) {
+    if (j == 0 && seg == 0 && threadIdx.x == 0) atomicOr(status + frame, 1);
+    return;
+  }
+  const int64_t rem = win.len - j * kRleChunk;              // the segment's bytes from this chunk's first one on
+  if (rem <= 0) return;                                     // (uniform) the segment has fewer chunks than the longest one
+  const int clen = rem < kRleChunk ? (int)rem : kRleChunk;
+  const unsigned char* src = win.seg + j * kRleChunk;
+  unsigned char held[kRlePer];                              // the lane's bytes, loaded back to back (one memory latency, not four)
+#pragma unroll
+  for (int k = 0; k < kRlePer; ++k) {
+    const int p = threadIdx.x + k * kRleThreads;
+    held[k] = src[p < clen ? p : clen - 1];
+  }
+#pragma unroll
+  for (int k = 0; k < kRlePer + 1; ++k) {
+    const int p = threadIdx.x + k * kRleThreads;
+    if (p >= kRleChunk + kRleEntries) break;
+    int nx = p, out = 0;
+    if (p < clen) rle_step(held[k < kRlePer ? k : 0], p, rem - 1 - p, nx, out);     // (p < clen <= kRleChunk: k < kRlePer)
+    s_next[p] = (unsigned short)nx;
+    s_out[p] = (unsigned)out;
+  }
+  __syncthreads();
+  for (int r = 0; r < kRleRounds; ++r) {
+    int nx[kRlePer];
+    unsigned add[kRlePer];
+#pragma unroll
+    for (int k = 0; k < kRlePer; ++k) {
+      const int a = s_next[threadIdx.x + k * kRleThreads];
+      nx[k] = s_next[a];
+      add[k] = s_out[a];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kRlePer; ++k) {
+      const int p = threadIdx.x + k * kRleThreads;
+      s_next[p] = (unsigned short)nx[k];
+      s_out[p] += add[k];
+    }
+    // the table asks for the 129 entry offsets alone: done once each of them has left the chunk (a chunk of literal runs
+    // takes nine steps, four rounds).  Lane e reads the word it has just written itself.
+    const int pending = threadIdx.x < kRleEntries && (int)s_next[threadIdx.x] < clen;
+    if (!__syncthreads_or(pending)) break;
+  }
+  if (threadIdx.x < kRleEntries) {
+    const int e = threadIdx.x;
+    const int ex = (int)s_next[e] - kRleChunk;              // (a short last chunk: nobody follows its exit)
+    table[(((frame * segments + seg) * n_chunks) + j) * kRleEntries + e] = (s_out[e] << 8) | (unsigned)(ex > 0 ? ex : 0);
+  }
+}
+
+// pass 2
+__global__ void __launch_bounds__(kRleThreads)
+rle_chain_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const int64_t* __restrict__ seg_off,
+                 const int64_t* __restrict__ seg_len, int segments, int64_t max_segment_bytes, int64_t n_chunks,
+                 int64_t samples, const unsigned* __restrict__ table, int64_t* __restrict__ chunk_off,
+                 unsigned char* __restrict__ chunk_entry, int32_t* __restrict__ status) {
+  __shared__ unsigned s_tab[kRleBatch * kRleEntries];
+  __shared__ int64_t s_off[kRleBatch];
+  __shared__ unsigned char s_entry[kRleBatch];
+  const int64_t frame = blockIdx.y;
+  const int seg = blockIdx.x;
+  const RleWindow win = rle_window(bytes, nbytes, seg_off, seg_len, frame, segments, seg, max_segment_bytes);
+  if (!win.ok) return;
+  const int64_t nck = (win.len + kRleChunk - 1) / kRleChunk, row0 = (frame * segments + seg) * n_chunks;
+  unsigned e = 0;                                           // (lane 0's: the chain)
+  int64_t off = 0;
+  for (int64_t b0 = 0; b0 < nck; b0 += kRleBatch) {
+    const int nb = nck - b0 < kRleBatch ? (int)(nck - b0) : kRleBatch;
+    const unsigned* rows = table + (row0 + b0) * kRleEntries;
+    for (int i = threadIdx.x; i < nb * kRleEntries; i += kRleThreads) s_tab[i] = rows[i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int k = 0; k < nb; ++k) {
+        s_entry[k] = (unsigned char)e;
+        s_off[k] = off;
+        const unsigned v = s_tab[k * kRleEntries + e];
+        e = v & 0xffu;
+        off += (int64_t)(v >> 8);                           // 64-bit: garbage may claim 128 output bytes per 2 input bytes
+      }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < nb; k += kRleThreads) {
+      chunk_entry[row0 + b0 + k] = s_entry[k];
+      chunk_off[row0 + b0 + k] = s_off[k];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && off != samples) atomicOr(status + frame, off < samples ? 2 : 4);
+}
+
+// pass 3
+__global__ void __launch_bounds__(kRleThreads)
+rle_expand_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const int64_t* __restrict__ seg_off,
+                  const int64_t* __restrict__ seg_len, int segments, int64_t max_segment_bytes, int64_t n_chunks,
+                  int64_t samples, const int64_t* __restrict__ chunk_off, const unsigned char* __restrict__ chunk_entry,
+                  unsigned char* __restrict__ native) {
+  __shared__ unsigned char s_in[kRleChunk + 128];           // the chunk and the literal bytes a run may take beyond it
+  __shared__ unsigned short s_lvl[kRleRounds][kRleChunk];   // level r: the control byte 2^r steps on (kRleChunk: none)
+  __shared__ unsigned char s_mark[kRleChunk];
+  __shared__ unsigned short s_run_pos[kRleChunk];
+  __shared__ unsigned s_run_off[kRleChunk];
+  __shared__ unsigned char s_run_len[kRleChunk];            // (stored as length - 1: 1 .. 128)
+  __shared__ unsigned long long s_w[kRleThreads / PL_WAVE];
+  __shared__ int s_runs;
+  const int64_t frame = blockIdx.z, j = blockIdx.x;
+  const int seg = blockIdx.y;
+  const RleWindow win = rle_window(bytes, nbytes, seg_off, seg_len, frame, segments, seg, max_segment_bytes);
+  if (!win.ok) return;
+  const int64_t rem = win.len - j * kRleChunk;
+  if (rem <= 0) return;
+  const int64_t row = (frame * segments + seg) * n_chunks + j;
+  const int clen = rem < kRleChunk ? (int)rem : kRleChunk;
+  const int staged = rem < kRleChunk + 128 ? (int)rem : kRleChunk + 128;
+  const unsigned char* src = win.seg + j * kRleChunk;
+  // the chunk's record and the lane's bytes, loaded back to back (one memory latency)
+  const int64_t off0 = chunk_off[row];
+  const int entry = chunk_entry[row];
+  unsigned char held[kRlePer + 1];
+#pragma unroll
+  for (int k = 0; k < kRlePer + 1; ++k) {
+    const int p = threadIdx.x + k * kRleThreads;
+    held[k] = src[p < staged ? p : staged - 1];
+  }
+  if (off0 >= samples) return;                              // (uniform) everything this chunk produces is dropped
+#pragma unroll
+  for (int k = 0; k < kRlePer + 1; ++k) {
+    const int p = threadIdx.x + k * kRleThreads;
+    if (p < staged) s_in[p] = held[k];
+  }
+  __syncthreads();
+  // a lane takes kRlePer CONSECUTIVE positions (the scan below runs over positions in order)
+  const int p0 = threadIdx.x * kRlePer;
+  int outs[kRlePer];
+#pragma unroll
+  for (int k = 0; k < kRlePer; ++k) {
+    const int p = p0 + k;
+    int nx = kRleChunk;
+    outs[k] = 0;
+    if (p < clen) rle_step(s_in[p], p, rem - 1 - p, nx, outs[k]);
+    s_lvl[0][p] = (unsigned short)(nx < clen ? nx : kRleChunk);
+    s_mark[p] = p == entry && p < clen ? 1 : 0;
+  }
+  __syncthreads();
+  // level r is needed while the walk from the entry makes more than 2^r steps inside the chunk (uniform: one LDS word)
+  int levels = 1;
+  for (int r = 1; r < kRleRounds && s_lvl[r - 1][entry] < kRleChunk; ++r) {
+#pragma unroll
+    for (int k = 0; k < kRlePer; ++k) {
+      const int a = s_lvl[r - 1][p0 + k];
+      s_lvl[r][p0 + k] = a < kRleChunk ? s_lvl[r - 1][a] : (unsigned short)kRleChunk;
+    }
+    __syncthreads();
+    levels = r + 1;
+  }
+  // before round r the marks are the walk's steps 0, 2^(r+1), 2 * 2^(r+1), ...; the round adds the steps half way between
+  // (a lane that sees a mark of this same round marks a position the walk visits as well: every mark is a true one)
+  for (int r = levels - 1; r >= 0; --r) {
+#pragma unroll
+    for (int k = 0; k < kRlePer; ++k) {
+      const int a = s_lvl[r][p0 + k];
+      if (s_mark[p0 + k] && a < kRleChunk) s_mark[a] = 1;
+    }
+    __syncthreads();
+  }
+  // runs that produce something, in order: (index, output offset) by one scan of (1, out) pairs
+  unsigned long long mine = 0;
+#pragma unroll
+  for (int k = 0; k < kRlePer; ++k)
+    if (s_mark[p0 + k] && outs[k] > 0) mine += ((unsigned long long)outs[k] << 32) | 1ull;
+  unsigned long long run = rle_block_exclusive(mine, s_w);
+#pragma unroll
+  for (int k = 0; k < kRlePer; ++k) {
+    if (s_mark[p0 + k] && outs[k] > 0) {
+      const unsigned idx = (unsigned)run;
+      s_run_pos[idx] = (unsigned short)(p0 + k);
+      s_run_off[idx] = (unsigned)(run >> 32);
+      s_run_len[idx] = (unsigned char)(outs[k] - 1);
+      run += ((unsigned long long)outs[k] << 32) | 1ull;
+    }
+  }
+  if (threadIdx.x == kRleThreads - 1) s_runs = (int)(unsigned)run;
+  __syncthreads();
+  const int n_runs = s_runs, g = threadIdx.x / kRleGroup, l = threadIdx.x % kRleGroup;
+  unsigned char* plane = native + frame * samples * segments + (segments - 1 - seg);
+  for (int q = g; q < n_runs; q += kRleThreads / kRleGroup) {
+    const int p = s_run_pos[q], n = (int)s_run_len[q] + 1;
+    const int64_t at = off0 + s_run_off[q];
+    const bool literal = s_in[p] < 128u;
+    for (int t = l; t < n; t += kRleGroup)
+      if (at + t < samples) plane[(at + t) * segments] = s_in[p + 1 + (literal ? t : 0)];
+  }
+}
+
+}  // namespace
+
+extern "C" int64_t pl_dicom_rle_work_bytes(int64_t n_frames, int segments, int64_t max_segment_bytes) {
+  if (n_frames < 1 || n_frames > 65535 || (segments != 1 && segments != 2 && segments != 4)) return -1;
+  if (max_segment_bytes < 0 || max_segment_bytes > ((int64_t)1 << 36)) return -1;
+  const int64_t n_chunks = pl_cdiv(max_segment_bytes > 0 ? max_segment_bytes : 1, kRleChunk);
+  const int64_t rows = n_frames * segments * n_chunks;
+  // chunk offsets (int64) | table (uint32 x 129) | chunk entries (uint8); every part 16-byte aligned
+  return ((rows * 8 + 15) & ~(int64_t)15) + ((rows * kRleEntries * 4 + 15) & ~(int64_t)15) + ((rows + 15) & ~(int64_t)15);
+}
+
+extern "C" int pl_dicom_rle_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_seg_off,
+                                   const int64_t* d_seg_len, int64_t n_frames, int segments, int64_t max_segment_bytes,
+                                   int rows, int cols, unsigned char* d_native, int32_t* d_status, unsigned char* d_work,
+                                   void* stream) {
+  if (segments != 1 && segments != 2 && segments != 4) {
+    pl_set_error("pl_dicom_rle_decode: unsupported segment count %d (BitsAllocated 8, 16 or 32 with SamplesPerPixel 1)", segments);
+    return PL_ERR_UNSUPPORTED;
+  }
+  PL_REQUIRE(d_bytes && d_seg_off && d_seg_len && d_native && d_status && d_work, "null pointer");
+  PL_REQUIRE(n_frames >= 1 && n_frames <= 65535, "1 <= n_frames <= 65535");
+  PL_REQUIRE(rows >= 1 && cols >= 1 && nbytes >= 0, "bad shape");
+  PL_REQUIRE(max_segment_bytes >= 0 && max_segment_bytes <= ((int64_t)1 << 36), "bad max_segment_bytes");
+  PL_REQUIRE(((uintptr_t)d_work & 15) == 0, "d_work must start on a 16-byte boundary");
+  const int64_t n_chunks = pl_cdiv(max_segment_bytes > 0 ? max_segment_bytes : 1, kRleChunk);
+  const int64_t table_rows = n_frames * segments * n_chunks, samples = (int64_t)rows * cols;
+  int64_t* chunk_off = reinterpret_cast<int64_t*>(d_work);
+  size_t at = (size_t)((table_rows * 8 + 15) & ~(int64_t)15);
+  unsigned* table = reinterpret_cast<unsigned*>(d_work + at);
+  at += (size_t)((table_rows * kRleEntries * 4 + 15) & ~(int64_t)15);
+  unsigned char* chunk_entry = d_work + at;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(d_status, 0, (size_t)n_frames * 4, st) != hipSuccess) {
+    pl_set_error("pl_dicom_rle_decode: memset failed");
+    return PL_ERR_HIP;
+  }
+  const dim3 blk(kRleThreads), per_chunk((unsigned)n_chunks, (unsigned)segments, (unsigned)n_frames);
+  hipLaunchKernelGGL(rle_table_kernel, per_chunk, blk, 0, st, d_bytes, nbytes, d_seg_off, d_seg_len, segments,
+                     max_segment_bytes, n_chunks, table, d_status);
+  hipLaunchKernelGGL(rle_chain_kernel, dim3((unsigned)segments, (unsigned)n_frames), blk, 0, st, d_bytes, nbytes, d_seg_off,
+                     d_seg_len, segments, max_segment_bytes, n_chunks, samples, table, chunk_off, chunk_entry, d_status);
+  hipLaunchKernelGGL(rle_expand_kernel, per_chunk, blk, 0, st, d_bytes, nbytes, d_seg_off, d_seg_len, segments,
+                     max_segment_bytes, n_chunks, samples, chunk_off, chunk_entry, d_native);
+  return pl_check_launch("pl_dicom_rle_decode");
+}

@@ -10,13 +10,23 @@ The reference gets ``pixel_array`` from pydicom (``pydicom>=2.0,<3``, pyproject.
 build reaches).  What is restated here is pydicom's documented native path -- ``numpy_handler.get_pixeldata``:
 ``np.frombuffer(PixelData[:expected_len], pixel_dtype(ds))`` reshaped to (NumberOfFrames, Rows, Columns) -- and the reading
 of a Part-10 stream as far as that path needs it (PS3.10 section 7.1 preamble + ``DICM``, PS3.5 section 7.1 data elements,
-explicit / implicit VR little endian and explicit VR big endian; sequences are skipped, never entered).  Compressed
-(encapsulated) transfer syntaxes belong to pydicom's codec plug-ins, not to this path: ``NotImplementedError``.
+explicit / implicit VR little endian and explicit VR big endian; sequences are skipped, never entered).
+
+One encapsulated transfer syntax is decoded here as well: RLE Lossless (1.2.840.10008.1.2.5; PS3.5 Annex G, section A.4.2),
+which pydicom decodes without a plug-in in a pure-Python byte loop (``rle_handler._rle_decode_segment``).  The item walk
+(Basic Offset Table, one fragment per frame, delimiter) and the 64-byte fragment headers are read on the host from the bytes
+it already holds; the files go to the device compressed, ``pl_dicom_rle_decode`` (``decode_rle_frames``: three passes over
+chunks of ``RLE_CHUNK`` input bytes, launches independent of N, nothing read back) expands the PackBits segments into the
+native little-endian frame buffer, and ``pl_dicom_decode`` takes that buffer wherever a conversion, a rescale or the
+unused-bit correction is asked for.  ``metadata.PixelDataFragments`` (our name, not pydicom's) lists the fragments as
+(offset, length).  The other compressed (encapsulated) transfer syntaxes and deflate belong to pydicom's codec plug-ins and
+reader, not to this path: ``NotImplementedError``.
 """
 from __future__ import annotations
 
 import io
 import struct
+import warnings
 from pathlib import Path
 
 import numpy as np
@@ -29,6 +39,10 @@ from .geometry import Point
 MM_PER_INCH = 25.4
 
 IMPLICIT_LE, EXPLICIT_LE, EXPLICIT_BE = "1.2.840.10008.1.2", "1.2.840.10008.1.2.1", "1.2.840.10008.1.2.2"
+RLE_LOSSLESS = "1.2.840.10008.1.2.5"
+RLE_CHUNK = 1024                                             # PL_DICOM_RLE_CHUNK: input bytes per chunk of the three passes
+_RLE_SHORT = "The amount of decoded RLE segment data doesn't match the expected amount"
+_RLE_PADDING = "The decoded RLE segment contains non-conformant padding"
 _LONG_VRS = {b"OB", b"OD", b"OF", b"OL", b"OV", b"OW", b"SQ", b"UC", b"UN", b"UR", b"UT", b"SV", b"UV"}
 
 # (group, element) -> (keyword, VR): the elements the image classes read (the VR column serves implicit-VR streams)
@@ -118,8 +132,37 @@ def _skip_undefined(buf: memoryview, pos: int, explicit: bool, big: bool) -> int
             pos, _, _, _, _ = _element(buf, pos, explicit, big)
 
 
-def _element(buf: memoryview, pos: int, explicit: bool, big: bool):
-    """One data element at ``pos`` -> (position after it, (group, element), VR or None, value offset, value length)."""
+def _fragments(buf: memoryview, pos: int, out: list) -> int:
+    """The items of an encapsulated Pixel Data value starting at ``pos`` (PS3.5 section A.4): the Basic Offset Table, then one
+    item per fragment, closed by (FFFE,E0DD) -> the position after the delimiter; ``out`` receives (offset, length) of every
+    fragment.  A filled Basic Offset Table must agree with the walk (RLE: one fragment per frame, section A.4.2)."""
+    n, table, tags = len(buf), None, []
+    while True:
+        if pos + 8 > n:
+            raise ValueError("malformed encapsulated Pixel Data: the sequence delimiter is missing")
+        g, el, ln = struct.unpack_from("<HHI", buf, pos)
+        if (g, el) == (0xFFFE, 0xE0DD):
+            break
+        if (g, el) != (0xFFFE, 0xE000) or ln == 0xFFFFFFFF or pos + 8 + ln > n:
+            raise ValueError("malformed encapsulated Pixel Data: an item of defined length inside the file was expected")
+        if table is None:
+            if ln % 4:
+                raise ValueError("malformed encapsulated Pixel Data: the Basic Offset Table is no list of uint32 values")
+            table = list(struct.unpack_from(f"<{ln // 4}I", buf, pos + 8))
+        else:
+            tags.append(pos)
+            out.append((pos + 8, ln))
+        pos += 8 + ln
+    if table is None:
+        raise ValueError("malformed encapsulated Pixel Data: the Basic Offset Table item is missing")
+    if table and table != [t - tags[0] for t in tags]:
+        raise ValueError("malformed encapsulated Pixel Data: the Basic Offset Table disagrees with the fragments that follow it")
+    return pos + 8
+
+
+def _element(buf: memoryview, pos: int, explicit: bool, big: bool, fragments: list | None = None):
+    """One data element at ``pos`` -> (position after it, (group, element), VR or None, value offset, value length).
+    ``fragments``: a list that receives the fragments of an encapsulated (7FE0,0010) -- RLE Lossless; None refuses them."""
     e = ">" if big else "<"
     g, el = struct.unpack_from(e + "HH", buf, pos)
     pos += 4
@@ -139,6 +182,8 @@ def _element(buf: memoryview, pos: int, explicit: bool, big: bool):
     start = pos
     if ln == 0xFFFFFFFF:
         if (g, el) == (0x7FE0, 0x0010):
+            if fragments is not None:
+                return _fragments(buf, pos, fragments), (g, el), vr, start, -1
             raise NotImplementedError("encapsulated (compressed) Pixel Data: decoded by pydicom's codec plug-ins, not by this path")
         return _skip_undefined(buf, pos, explicit, big), (g, el), vr, start, -1
     return pos + ln, (g, el), vr, start, ln
@@ -147,7 +192,8 @@ def _element(buf: memoryview, pos: int, explicit: bool, big: bool):
 def read_part10(source) -> tuple[Metadata, np.ndarray]:
     """``pydicom.dcmread(source, force=True)`` as far as the image classes need it -> (metadata, the file's bytes as a uint8
     array).  ``metadata.PixelData`` (``FloatPixelData`` / ``DoubleFloatPixelData``) is the pair (offset, length) of the value
-    inside those bytes -- the samples are never copied on the host."""
+    inside those bytes -- the samples are never copied on the host.  RLE Lossless: ``PixelData`` is (offset, -1) and
+    ``metadata.PixelDataFragments`` the list of (offset, length) of the fragments."""
     if isinstance(source, (bytes, bytearray, memoryview, np.ndarray)):
         data = np.frombuffer(bytes(source) if not isinstance(source, np.ndarray) else source.tobytes(), dtype=np.uint8)
     elif isinstance(source, (str, Path)):
@@ -173,8 +219,11 @@ def read_part10(source) -> tuple[Metadata, np.ndarray]:
         explicit, big = True, False                         # every encapsulated syntax is explicit VR little endian
     else:
         explicit, big = ts != IMPLICIT_LE, ts == EXPLICIT_BE
+    fragments = [] if ts == RLE_LOSSLESS else None
     while pos + 8 <= n:
-        pos, tag, vr, start, ln = _element(buf, pos, explicit, big)
+        pos, tag, vr, start, ln = _element(buf, pos, explicit, big, fragments)
+        if tag == (0x7FE0, 0x0010) and ln < 0:
+            values["PixelData"], values["PixelDataFragments"] = (start, -1), fragments
         if tag not in _TAGS or ln < 0:
             continue
         key, table_vr = _TAGS[tag]
@@ -244,6 +293,91 @@ def decode_frames(file_bytes, offsets, rows: int, cols: int, bits_allocated: int
     return res
 
 
+def _index(a, dev) -> torch.Tensor:
+    if isinstance(a, torch.Tensor):
+        return a.to(device=dev, dtype=torch.int64).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+
+
+def decode_rle_frames(file_bytes, seg_off, seg_len, rows: int, cols: int, bits_allocated: int, bits_stored: int | None = None,
+                      pixel_representation: int = 0, correct_unused_bits: bool = False, out: str = "container", rescale=None,
+                      device=None, max_segment_bytes: int | None = None, native: torch.Tensor | None = None) -> torch.Tensor:
+    """``pl_dicom_rle_decode``, the RLE Lossless counterpart of ``decode_frames``: N frames whose PackBits segments lie
+    anywhere inside ``file_bytes`` (uint8 array / tensor; device tensors are used in place); ``seg_off`` / ``seg_len`` are
+    int64 [N, BitsAllocated / 8]: segment s of a frame (the most significant byte plane first) is ``seg_len[f, s]`` bytes at
+    byte ``seg_off[f, s]``.  -> device tensor [N, rows, cols] exactly as ``decode_frames`` gives it for the same frames
+    stored native (``out``, ``rescale``, ``correct_unused_bits``: the decoded little-endian buffer goes through
+    ``pl_dicom_decode``; the plain container dtype IS that buffer, returned as a view).  ``_pl_status`` int32 [N]: bit 0 a
+    segment window outside the buffer (the frame is left untouched), bit 1 a segment decoded to fewer than rows * cols
+    bytes, bit 2 to more (the frame is complete).  ``max_segment_bytes``: an upper bound of ``seg_len`` (taken from a host
+    array when absent; a device tensor is reduced and read back once).  ``native``: a uint8 device tensor
+    [N, rows * cols * BitsAllocated / 8] to decode into."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    bits, rep = int(bits_allocated), int(pixel_representation)
+    cont = {(8, 0): torch.uint8, (8, 1): torch.int8, (16, 0): torch.uint16, (16, 1): torch.int16, (32, 0): torch.uint32,
+            (32, 1): torch.int32}[(bits, rep)]
+    segments = bits // 8
+    if max_segment_bytes is None:
+        max_segment_bytes = int(seg_len.max()) if isinstance(seg_len, torch.Tensor) else int(np.max(seg_len, initial=0))
+    if not isinstance(file_bytes, torch.Tensor):
+        held = np.ascontiguousarray(file_bytes, dtype=np.uint8)
+        file_bytes = torch.from_numpy(held if held.flags.writeable else held.copy())
+    buf = file_bytes.to(device=dev, dtype=torch.uint8).contiguous()
+    so, sl = _index(seg_off, dev).reshape(-1, segments), _index(seg_len, dev).reshape(-1, segments)
+    n = int(so.shape[0])
+    if so.shape != sl.shape:
+        raise ValueError("decode_rle_frames: seg_off and seg_len must both be [N, BitsAllocated / 8]")
+    frame_bytes = rows * cols * segments
+    if native is None:
+        native = torch.empty((n, frame_bytes), dtype=torch.uint8, device=dev)
+    elif native.dtype != torch.uint8 or tuple(native.shape) != (n, frame_bytes) or not native.is_contiguous() or not native.is_cuda:
+        raise ValueError("decode_rle_frames: native must be a contiguous uint8 device tensor [N, rows * cols * BitsAllocated / 8]")
+    lib = _lib.load()
+    nwork = int(lib.pl_dicom_rle_work_bytes(n, segments, int(max_segment_bytes)))
+    work = torch.empty(max(nwork, 16), dtype=torch.uint8, device=dev)
+    status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    check(lib.pl_dicom_rle_decode(buf.data_ptr(), buf.numel(), so.data_ptr(), sl.data_ptr(), n, segments, int(max_segment_bytes),
+                                  rows, cols, native.data_ptr(), status.data_ptr(), work.data_ptr(),
+                                  torch.cuda.current_stream(dev).cuda_stream), "pl_dicom_rle_decode")
+    stored = bits if bits_stored is None else int(bits_stored)
+    if out == "container" and not (correct_unused_bits and stored < bits):
+        res = native.view(cont).reshape(n, rows, cols)
+    else:
+        res = decode_frames(native.reshape(-1), torch.arange(n, dtype=torch.int64, device=dev) * frame_bytes, rows, cols, bits,
+                            stored, rep, big_endian=False, correct_unused_bits=correct_unused_bits, out=out, rescale=rescale,
+                            device=dev)
+    res._pl_status = status[:n]
+    return res
+
+
+def _rle_segments(buf: np.ndarray, fragment: tuple, segments: int, name: str):
+    """The 64-byte header of one RLE fragment (PS3.5 section G.5: the number of segments, then 15 offsets from the start of the
+    header) -> [(offset inside ``buf``, length)] of its segments; ``ValueError`` for a header that is malformed."""
+    off, ln = fragment
+    if ln < 64:
+        raise ValueError(f"{name}: the RLE fragment is shorter than its 64-byte header")
+    head = struct.unpack_from("<16I", buf, off)
+    if head[0] != segments:
+        raise ValueError(f"{name}: the RLE header states {head[0]} segments where BitsAllocated / 8 = {segments} are expected")
+    offs = list(head[1:1 + segments])
+    if any(b <= a for a, b in zip(offs, offs[1:])):
+        raise ValueError(f"{name}: the segment offsets of the RLE header are not strictly increasing")
+    if offs[-1] > ln:
+        raise ValueError(f"{name}: a segment offset of the RLE header lies outside the fragment")
+    return [(off + a, b - a) for a, b in zip(offs, offs[1:] + [ln])]
+
+
+def _check_rle_status(status: torch.Tensor, owner, names) -> None:
+    """pydicom's answers to the status of ``decode_rle_frames`` (one transfer): ``ValueError`` for the first frame with a
+    short segment (or a window outside the buffer), one warning for segments that decoded to more than the plane."""
+    flags = status.cpu().numpy()
+    bad = np.flatnonzero(flags & 3)
+    if bad.size:
+        raise ValueError(f"{_RLE_SHORT} ({names[owner[int(bad[0])]]}, frame {int(bad[0])} of the stack)")
+    if (flags & 4).any():
+        warnings.warn(f"{_RLE_PADDING} ({names[owner[int(np.flatnonzero(flags & 4)[0])]]})")
+
+
 def _check_status(frames: torch.Tensor) -> torch.Tensor:
     st = getattr(frames, "_pl_status", None)
     if st is not None and bool(st.any()):
@@ -255,12 +389,14 @@ def _check_status(frames: torch.Tensor) -> torch.Tensor:
 def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bool | None = None,
                 correct_unused_bits: bool = False, device=None, check: bool = True):
     """The batched loader: Part-10 files (paths, bytes or file objects; every file may hold several frames) of ONE pixel
-    format and frame size -> (device tensor [N, H, W], list of per-file metadata).  Per file exactly what
-    ``DicomImage.__init__`` does (image.py:1431-1444): ``pixel_array`` [``.astype(dtype)``] then ``_rescale_dicom_values``;
+    format, frame size and kind (all native or all RLE Lossless) -> (device tensor [N, H, W], list of per-file metadata).  Per
+    file exactly what ``DicomImage.__init__`` does (image.py:1431-1444): ``pixel_array`` [``.astype(dtype)``] then
+    ``_rescale_dicom_values``;
     files with both rescale tags take the fused float64 form of the kernel when every file carries the SAME slope and
     intercept (a series), otherwise the frames are decoded once and rescaled file by file."""
     from .image import rescale_dicom_values
 
+    sources = list(sources)
     metas, blobs = [], []
     for s in sources:
         m, b = read_part10(s)
@@ -271,12 +407,26 @@ def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bo
     for l in lay[1:]:
         if (l[0], l[4], l[5], l[6]) != (tdt, rows, cols, big):
             raise ValueError("load_frames: the files differ in pixel format or frame size (the reference's stacks refuse that too)")
-    # one host buffer, every file at a 4-byte boundary; frame offsets inside it
+    rle = ["PixelDataFragments" in m for m in metas]
+    if any(rle) and not all(rle):
+        raise ValueError("load_frames: native and RLE Lossless files are mixed; load the two kinds separately")
+    rle = all(rle) and bool(metas)
+    names = [f"file {k}" + (f" ({s})" if isinstance(s, (str, Path)) else "") for k, s in enumerate(sources)]
+    # one host buffer, every file at a 4-byte boundary; frame offsets (RLE: segment windows) inside it
     starts, offsets, owner, pos = [], [], [], 0
     for k, (b, l) in enumerate(zip(blobs, lay)):
         starts.append(pos)
         off, ln = l[7]
         frames = l[3]
+        if rle:
+            found = metas[k].PixelDataFragments
+            if len(found) != frames:
+                raise ValueError(f"{names[k]}: {len(found)} RLE fragments for NumberOfFrames = {frames} (one fragment per frame)")
+            for frag in found:
+                offsets.append([(pos + o, n) for o, n in _rle_segments(b, frag, ib, names[k])])
+                owner.append(k)
+            pos += (len(b) + 3) & ~3
+            continue
         expected = frames * rows * cols * ib
         if ln < expected:
             raise ValueError(f"The length of the pixel data in the dataset ({ln} bytes) doesn't match the expected length "
@@ -292,29 +442,49 @@ def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bo
     rep = int(metas[0].PixelRepresentation)
     common = dict(rows=rows, cols=cols, bits_allocated=ib * 8, bits_stored=stored, pixel_representation=rep, big_endian=big,
                   correct_unused_bits=correct_unused_bits, device=device)
+    if rle:                                                  # the same calls, the RLE kernels in front of pl_dicom_decode
+        del common["big_endian"]
+        windows = np.asarray(offsets, dtype=np.int64).reshape(-1, ib, 2)
+        seg_off, seg_len = np.ascontiguousarray(windows[:, :, 0]), np.ascontiguousarray(windows[:, :, 1])
+
+        seen = []
+
+        def decode(**kw):
+            x = decode_rle_frames(host, seg_off, seg_len, max_segment_bytes=int(seg_len.max(initial=0)), **common, **kw)
+            seen.append(x._pl_status)                        # (an integer astype hands on a tensor without it)
+            return x
+
+        def verify(x):
+            _check_rle_status(seen[-1], owner, names)
+            return x
+    else:
+        def decode(**kw):
+            return decode_frames(host, offsets, **common, **kw)
+
+        verify = _check_status
     has_rescale = [("RescaleSlope" in m and "RescaleIntercept" in m) for m in metas]
     same = all(has_rescale) and len({(m.RescaleSlope, m.RescaleIntercept) for m in metas}) == 1
     inverts = [bool(invert_pixels or (invert_pixels is None and m.get("PixelIntensityRelationshipSign") == -1)) for m in metas]
     np_dt = None if dtype is None else np.dtype(dtype)
     if raw_pixels or not any(has_rescale):
         if np_dt is None:
-            x = decode_frames(host, offsets, out="container", **common)
+            x = decode(out="container")
         elif np_dt in _NP_TO_TORCH:
-            x = decode_frames(host, offsets, out={4: "float32", 8: "float64"}[np_dt.itemsize], **common)
+            x = decode(out={4: "float32", 8: "float64"}[np_dt.itemsize])
         else:
-            x = _astype(decode_frames(host, offsets, out="container", **common), np_dt)
+            x = _astype(decode(out="container"), np_dt)
         if check:
-            _check_status(x)
+            verify(x)
     elif same and np_dt in (None, np.dtype(np.float64)):
-        x = decode_frames(host, offsets, out="float64", rescale=(metas[0].RescaleSlope, metas[0].RescaleIntercept), **common)
+        x = decode(out="float64", rescale=(metas[0].RescaleSlope, metas[0].RescaleIntercept))
         if check:
-            _check_status(x)
+            verify(x)
     else:
         if not all(has_rescale):
             raise ValueError("load_frames: some files carry rescale tags and some do not; load them separately")
-        base = decode_frames(host, offsets, out="container", **common)
+        base = decode(out="container")
         if check:
-            _check_status(base)
+            verify(base)
         if np_dt is not None:
             base = _astype(base, np_dt)
         own = np.asarray(owner)
