@@ -572,6 +572,34 @@ int pl_dicom_rle_decode(const unsigned char* d_bytes, int64_t nbytes, const int6
                         int64_t n_frames, int segments, int64_t max_segment_bytes, int rows, int cols,
                         unsigned char* d_native, int32_t* d_status, unsigned char* d_work, void* stream);
 
+/* ---- f1 ("next" row), the TIFF half: strip TIFFs of scanned film -> typed frames ----------------------------------
+ * `np.asarray(PIL.Image.open(f))` (libtiff) for a STACK of classic strip TIFFs of one width, height, BitsPerSample and
+ * SamplesPerPixel whose files lie anywhere inside one device buffer (copied as they are, compressed).  The host walks the
+ * IFDs; the device sees strips: strip s is the d_strip_len[s] bytes at byte d_strip_off[s] (int64 [n_strips], any
+ * alignment) and d_strip_desc int32 [n_strips][4] = frame, first row, rows, Compression (1 none, 32773 PackBits, 5 LZW
+ * new-style with early change) says where its rows go.  d_frame_flags int32 [n_frames]: bit 0 Predictor 2 (horizontal
+ * differencing; per channel, in the sample width, after the byte swap), bit 1 big-endian ("MM") 16-bit samples.
+ *   bits / samples_per_pixel: 8 or 16 / 1 (grey) or 8 / 3 (RGB, PlanarConfiguration 1), else unsupported;
+ *   compressions: a mask of what the strips use, 1 none | 2 PackBits | 4 LZW (launches for the others are left out; a strip
+ *   of a compression outside the mask is flagged); max_strip_bytes: an upper bound of every d_strip_len;
+ *   out_kind 0: d_out [n_frames][height][width] in the container dtype (uint8, uint16; RGB: int32
+ *   (19595 R + 38470 G + 7471 B + 0x8000) >> 16, PIL's convert("I")), 1: uint16, 2: float64 (`array.astype(dtype)`);
+ *   d_status int32 [n_frames] (zeroed here), per frame: bit 0 a strip descriptor is unsound or its window does not lie inside
+ *   [0, nbytes) or is longer than max_strip_bytes (such a strip is never read and NOTHING of its frame is stored), bit 1 a
+ *   strip decoded to fewer than rows x row bytes (PIL raises OSError), bit 2 an LZW code names an entry that does not exist
+ *   (PIL: OSError, decoder error -2).  A flagged frame does not disturb the others.  Rows no strip covers are undefined.
+ *   d_work: pl_tiff_work_bytes() bytes on a 16-byte boundary (-1 for arguments pl_tiff_decode refuses).
+ * The number of launches (at most seven) does not depend on n_frames or n_strips and nothing is read back.  PackBits strips
+ * go through the passes of pl_dicom_rle_decode (a strip is one stream; n_strips <= 65535 then); an LZW strip is one wave's
+ * work.  1 <= n_frames <= 65535, n_strips >= 1, a frame below 2 GiB, non-null pointers, d_bytes on a 4-byte boundary (else
+ * invalid argument): checked before any launch. */
+int64_t pl_tiff_work_bytes(int64_t n_frames, int64_t n_strips, int64_t max_strip_bytes, int width, int height, int bits,
+                           int samples_per_pixel, int compressions);
+int pl_tiff_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_strip_off, const int64_t* d_strip_len,
+                   const int32_t* d_strip_desc, int64_t n_strips, int64_t max_strip_bytes, const int32_t* d_frame_flags,
+                   int64_t n_frames, int width, int height, int bits, int samples_per_pixel, int compressions, void* d_out,
+                   int out_kind, int32_t* d_status, unsigned char* d_work, void* stream);
+
 /* ---- f2 ("next" row, first half): skimage.feature.canny as called at pylinac/planar_imaging.py:574-588 -------
  * float64 images, mask=None.  The caller composes: G = pl_gaussian2d_mode(mode 2) of the image and of an all-ones
  * frame; pl_canny_normalise: smoothed = G(image) / (G(ones) + eps); pl_sobel on axis 1 (jsobel) and axis 0 (isobel);

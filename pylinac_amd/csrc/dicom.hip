@@ -309,7 +309,7 @@ __device__ __forceinline__ U rle_block_exclusive(U mine, U* s_w) {
 __global__ void __launch_bounds__(kRleThreads)
 rle_table_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const int64_t* __restrict__ seg_off,
                  const int64_t* __restrict__ seg_len, int segments, int64_t max_segment_bytes, int64_t n_chunks,
-                 unsigned* __restrict__ table, int32_t* __restrict__ status) {
+                 unsigned* __restrict__ table, int32_t* __restrict__ status, PlPackbitsGeom geom) {
   // nodes 0 .. kRleChunk + 128: a node at or beyond the chunk's bytes is an exit (it points at itself and produces nothing)
   __shared__ unsigned short s_next[kRleChunk + kRleEntries];
   __shared__ unsigned s_out[kRleChunk + kRleEntries];
@@ -317,7 +317,7 @@ rle_table_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const 
   const int seg = blockIdx.y;
   const RleWindow win = rle_window(bytes, nbytes, seg_off, seg_len, frame, segments, seg, max_segment_bytes);
   if (!win.ok) {
-    if (j == 0 && seg == 0 && threadIdx.x == 0) atomicOr(status + frame, 1);
+    if (j == 0 && seg == 0 && threadIdx.x == 0) atomicOr(status + (geom.status_index ? geom.status_index[frame] : frame), 1);
     return;
   }
   const int64_t rem = win.len - j * kRleChunk;              // the segment's bytes from this chunk's first one on
@@ -373,7 +373,7 @@ __global__ void __launch_bounds__(kRleThreads)
 rle_chain_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const int64_t* __restrict__ seg_off,
                  const int64_t* __restrict__ seg_len, int segments, int64_t max_segment_bytes, int64_t n_chunks,
                  int64_t samples, const unsigned* __restrict__ table, int64_t* __restrict__ chunk_off,
-                 unsigned char* __restrict__ chunk_entry, int32_t* __restrict__ status) {
+                 unsigned char* __restrict__ chunk_entry, int32_t* __restrict__ status, PlPackbitsGeom geom) {
   __shared__ unsigned s_tab[kRleBatch * kRleEntries];
   __shared__ int64_t s_off[kRleBatch];
   __shared__ unsigned char s_entry[kRleBatch];
@@ -405,6 +405,10 @@ rle_chain_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const 
     }
     __syncthreads();
   }
+  if (geom.expect) {                                        // streams of another container: short is all they report
+    if (threadIdx.x == 0 && off < geom.expect[frame]) atomicOr(status + geom.status_index[frame], 2);
+    return;
+  }
   if (threadIdx.x == 0 && off != samples) atomicOr(status + frame, off < samples ? 2 : 4);
 }
 
@@ -413,7 +417,7 @@ __global__ void __launch_bounds__(kRleThreads)
 rle_expand_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const int64_t* __restrict__ seg_off,
                   const int64_t* __restrict__ seg_len, int segments, int64_t max_segment_bytes, int64_t n_chunks,
                   int64_t samples, const int64_t* __restrict__ chunk_off, const unsigned char* __restrict__ chunk_entry,
-                  unsigned char* __restrict__ native) {
+                  unsigned char* __restrict__ native, PlPackbitsGeom geom) {
   __shared__ unsigned char s_in[kRleChunk + 128];           // the chunk and the literal bytes a run may take beyond it
   __shared__ unsigned short s_lvl[kRleRounds][kRleChunk];   // level r: the control byte 2^r steps on (kRleChunk: none)
   __shared__ unsigned char s_mark[kRleChunk];
@@ -428,6 +432,7 @@ rle_expand_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const
   if (!win.ok) return;
   const int64_t rem = win.len - j * kRleChunk;
   if (rem <= 0) return;
+  if (geom.expect) samples = geom.expect[frame];            // (uniform) the stream's own output size
   const int64_t row = (frame * segments + seg) * n_chunks + j;
   const int clen = rem < kRleChunk ? (int)rem : kRleChunk;
   const int staged = rem < kRleChunk + 128 ? (int)rem : kRleChunk + 128;
@@ -501,7 +506,7 @@ rle_expand_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const
   if (threadIdx.x == kRleThreads - 1) s_runs = (int)(unsigned)run;
   __syncthreads();
   const int n_runs = s_runs, g = threadIdx.x / kRleGroup, l = threadIdx.x % kRleGroup;
-  unsigned char* plane = native + frame * samples * segments + (segments - 1 - seg);
+  unsigned char* plane = geom.dst ? native + geom.dst[frame] : native + frame * samples * segments + (segments - 1 - seg);
   for (int q = g; q < n_runs; q += kRleThreads / kRleGroup) {
     const int p = s_run_pos[q], n = (int)s_run_len[q] + 1;
     const int64_t at = off0 + s_run_off[q];
@@ -522,6 +527,36 @@ extern "C" int64_t pl_dicom_rle_work_bytes(int64_t n_frames, int segments, int64
   return ((rows * 8 + 15) & ~(int64_t)15) + ((rows * kRleEntries * 4 + 15) & ~(int64_t)15) + ((rows + 15) & ~(int64_t)15);
 }
 
+// the three launches over validated arguments (d_work: pl_dicom_rle_work_bytes() bytes, 16-byte aligned)
+static void rle_launch(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_seg_off, const int64_t* d_seg_len,
+                       int64_t n_frames, int segments, int64_t max_segment_bytes, int64_t samples, unsigned char* d_native,
+                       int32_t* d_status, unsigned char* d_work, PlPackbitsGeom geom, hipStream_t st) {
+  const int64_t n_chunks = pl_cdiv(max_segment_bytes > 0 ? max_segment_bytes : 1, kRleChunk);
+  const int64_t table_rows = n_frames * segments * n_chunks;
+  int64_t* chunk_off = reinterpret_cast<int64_t*>(d_work);
+  size_t at = (size_t)((table_rows * 8 + 15) & ~(int64_t)15);
+  unsigned* table = reinterpret_cast<unsigned*>(d_work + at);
+  at += (size_t)((table_rows * kRleEntries * 4 + 15) & ~(int64_t)15);
+  unsigned char* chunk_entry = d_work + at;
+  const dim3 blk(kRleThreads), per_chunk((unsigned)n_chunks, (unsigned)segments, (unsigned)n_frames);
+  hipLaunchKernelGGL(rle_table_kernel, per_chunk, blk, 0, st, d_bytes, nbytes, d_seg_off, d_seg_len, segments,
+                     max_segment_bytes, n_chunks, table, d_status, geom);
+  hipLaunchKernelGGL(rle_chain_kernel, dim3((unsigned)segments, (unsigned)n_frames), blk, 0, st, d_bytes, nbytes, d_seg_off,
+                     d_seg_len, segments, max_segment_bytes, n_chunks, samples, table, chunk_off, chunk_entry, d_status, geom);
+  hipLaunchKernelGGL(rle_expand_kernel, per_chunk, blk, 0, st, d_bytes, nbytes, d_seg_off, d_seg_len, segments,
+                     max_segment_bytes, n_chunks, samples, chunk_off, chunk_entry, d_native, geom);
+}
+
+// the same passes for PackBits streams of another container (pl_common.h: tiff.hip's strips); no argument is checked here
+int64_t pl_packbits_work_bytes(int64_t n_streams, int64_t max_stream_bytes) {
+  return pl_dicom_rle_work_bytes(n_streams, 1, max_stream_bytes);
+}
+void pl_packbits_expand(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_off, const int64_t* d_len,
+                        int64_t n_streams, int64_t max_stream_bytes, unsigned char* d_out, int32_t* d_status,
+                        unsigned char* d_work, PlPackbitsGeom geom, hipStream_t st) {
+  rle_launch(d_bytes, nbytes, d_off, d_len, n_streams, 1, max_stream_bytes, 0, d_out, d_status, d_work, geom, st);
+}
+
 extern "C" int pl_dicom_rle_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_seg_off,
                                    const int64_t* d_seg_len, int64_t n_frames, int segments, int64_t max_segment_bytes,
                                    int rows, int cols, unsigned char* d_native, int32_t* d_status, unsigned char* d_work,
@@ -535,24 +570,12 @@ extern "C" int pl_dicom_rle_decode(const unsigned char* d_bytes, int64_t nbytes,
   PL_REQUIRE(rows >= 1 && cols >= 1 && nbytes >= 0, "bad shape");
   PL_REQUIRE(max_segment_bytes >= 0 && max_segment_bytes <= ((int64_t)1 << 36), "bad max_segment_bytes");
   PL_REQUIRE(((uintptr_t)d_work & 15) == 0, "d_work must start on a 16-byte boundary");
-  const int64_t n_chunks = pl_cdiv(max_segment_bytes > 0 ? max_segment_bytes : 1, kRleChunk);
-  const int64_t table_rows = n_frames * segments * n_chunks, samples = (int64_t)rows * cols;
-  int64_t* chunk_off = reinterpret_cast<int64_t*>(d_work);
-  size_t at = (size_t)((table_rows * 8 + 15) & ~(int64_t)15);
-  unsigned* table = reinterpret_cast<unsigned*>(d_work + at);
-  at += (size_t)((table_rows * kRleEntries * 4 + 15) & ~(int64_t)15);
-  unsigned char* chunk_entry = d_work + at;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(d_status, 0, (size_t)n_frames * 4, st) != hipSuccess) {
     pl_set_error("pl_dicom_rle_decode: memset failed");
     return PL_ERR_HIP;
   }
-  const dim3 blk(kRleThreads), per_chunk((unsigned)n_chunks, (unsigned)segments, (unsigned)n_frames);
-  hipLaunchKernelGGL(rle_table_kernel, per_chunk, blk, 0, st, d_bytes, nbytes, d_seg_off, d_seg_len, segments,
-                     max_segment_bytes, n_chunks, table, d_status);
-  hipLaunchKernelGGL(rle_chain_kernel, dim3((unsigned)segments, (unsigned)n_frames), blk, 0, st, d_bytes, nbytes, d_seg_off,
-                     d_seg_len, segments, max_segment_bytes, n_chunks, samples, table, chunk_off, chunk_entry, d_status);
-  hipLaunchKernelGGL(rle_expand_kernel, per_chunk, blk, 0, st, d_bytes, nbytes, d_seg_off, d_seg_len, segments,
-                     max_segment_bytes, n_chunks, samples, chunk_off, chunk_entry, d_native);
+  rle_launch(d_bytes, nbytes, d_seg_off, d_seg_len, n_frames, segments, max_segment_bytes, (int64_t)rows * cols, d_native,
+             d_status, d_work, PlPackbitsGeom{nullptr, nullptr, nullptr}, st);
   return pl_check_launch("pl_dicom_rle_decode");
 }

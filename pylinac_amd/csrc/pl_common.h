@@ -28,6 +28,20 @@ int pl_cu_count();
 // The "opt in to more than 64 KB of dynamic LDS" flags next to the launches are std::atomic: hipFuncSetAttribute is
 // idempotent, so two host threads racing through a first call both set it and both store `true` -- no data race.
 
+// PackBits streams of another container through dicom.hip's three chunked passes (the one PackBits scanner of the library):
+// stream i is the d_len[i] bytes at d_off[i] (validated by the caller, each <= max_stream_bytes; a length of 0 is skipped),
+// its first expect[i] decoded bytes go to d_out + dst[i] as they come, and a stream that decodes to fewer sets bit 1 (value 2)
+// of d_status[status_index[i]].  n_streams <= 65535; d_work: pl_packbits_work_bytes() bytes on a 16-byte boundary.
+struct PlPackbitsGeom {                                     // all null: the DICOM layout of pl_dicom_rle_decode
+  const int64_t* expect;
+  const int64_t* dst;
+  const int32_t* status_index;
+};
+int64_t pl_packbits_work_bytes(int64_t n_streams, int64_t max_stream_bytes);
+void pl_packbits_expand(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_off, const int64_t* d_len,
+                        int64_t n_streams, int64_t max_stream_bytes, unsigned char* d_out, int32_t* d_status,
+                        unsigned char* d_work, PlPackbitsGeom geom, hipStream_t st);
+
 // ---- device side -----------------------------------------------------------------------------
 // scipy 'reflect' (half-sample symmetric:  d c b a | a b c d | d c b a), valid for any distance.
 __device__ __forceinline__ int pl_reflect(int i, int n) {
