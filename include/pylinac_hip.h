@@ -958,7 +958,8 @@ int pl_colparts_profile_fwxm(const uint32_t* d_parts, int64_t n, int bands, int 
  * for bit.  d_ws: uint64 [n][w + 1] (column sums + arrival ticket of each frame), ALL ZERO on entry and all zero again when the
  * launch has run: zero it once, when it is allocated, and give it to one launch at a time.  Frames as
  * pl_median3_threshold_colsum_u16 (h > 1, w % 8 == 0, 16-byte aligned planes) and a search region whose tables fit 48 KiB of
- * LDS (up to ~3 000 samples): pl_median3_threshold_profile_fwxm_covers(h, w, params) == 1; PL_ERR_INVALID_ARG otherwise. */
+ * LDS (up to ~3 000 samples), frames of fewer than 2^31 bytes: pl_median3_threshold_profile_fwxm_covers(h, w, params) == 1;
+ * PL_ERR_INVALID_ARG otherwise. */
 int pl_median3_threshold_profile_fwxm_u16(const uint16_t* in, uint16_t* out, int64_t n, int h, int w, const int32_t* d_thr,
                                           const pl_peak_params* params, int cap, double* d_profile, int32_t* d_count,
                                           int32_t* d_idx, int32_t* d_left_base, int32_t* d_right_base, double* d_props,
@@ -967,7 +968,8 @@ int pl_median3_threshold_profile_fwxm_u16(const uint16_t* in, uint16_t* out, int
 /* The same launch, told what it need not read: d_cellmax uint16 [n][ceil(h / 32)][ceil(w / 64)], every entry >= the largest 3x3
  * median of its cell of `in` (pl_median3_otsu16_cells of the same plane; 65535 = no knowledge).  Cells whose entry lies below
  * the frame's threshold are stored as zeros without being read.  Every output as pl_median3_threshold_profile_fwxm_u16, bit
- * for bit. */
+ * for bit.  Frames of 2^31 bytes or more (h * w * 2: the launch addresses a frame through a bounded buffer resource) are
+ * PL_ERR_INVALID_ARG here and "not covered" for pl_median3_threshold_profile_fwxm_covers. */
 int pl_median3_threshold_profile_fwxm_cells_u16(const uint16_t* in, uint16_t* out, int64_t n, int h, int w, const int32_t* d_thr,
                                                 const uint16_t* d_cellmax, const pl_peak_params* params, int cap,
                                                 double* d_profile, int32_t* d_count, int32_t* d_idx, int32_t* d_left_base,

@@ -21,7 +21,13 @@
 // `load` = false: the lane issues NO load and digests zeros; its medians, and the outer columns of its two neighbours'
 // blocks, are then meaningless -- for callers that know beforehand which lanes' medians they will not use (a lane whose
 // medians ARE used needs `load` in itself and in both neighbours).
-template <typename T, int ROWS, int AHEAD = 4, typename F>
+// BYOFFSET: the form for a `load` that is a RUN-TIME predicate.  Block and edge column are raw buffer loads from a resource
+// bounded to the frame, and a lane that must not load gets an offset no frame holds (kPlBufferNowhere): the hardware drops
+// the access -- zeros, no traffic -- and no load sits under a branch.  With `if (load)` around them the compiler cannot count
+// the ring's outstanding loads across the branch and drains the queue (s_waitcnt vmcnt(0): the look-ahead load issued a
+// moment ago included, a full memory round trip about every AHEAD rows); by offset the walk waits with a counted vmcnt again.
+// Needs a frame of fewer than 2^31 bytes (pl_median3_rows_bounded_covers).  The other form compiles to what it was.
+template <typename T, int ROWS, int AHEAD = 4, bool BYOFFSET = false, typename F>
 __device__ __forceinline__ void pl_median3_rows(const T* __restrict__ f, int h, int w, int c0, int lane, int r0_lane, F&& consume,
                                                 bool load = true) {
   static_assert(sizeof(T) == 2, "16-bit dtypes");
@@ -34,13 +40,24 @@ __device__ __forceinline__ void pl_median3_rows(const T* __restrict__ f, int h, 
   const bool edge = edge_l || edge_r;
   const unsigned offe = edge_l ? offc - 2u : offc + 16u;
   struct Raw { uint4 q; int e; };
+  [[maybe_unused]] __amdgpu_buffer_rsrc_t rs;
+  [[maybe_unused]] unsigned voffq = 0, voffe = 0;
+  if constexpr (BYOFFSET) {
+    rs = pl_make_rsrc_bounded(f, (unsigned)h * (unsigned)w * 2u);
+    voffq = load ? offc : kPlBufferNowhere;
+    voffe = load && edge ? offe : kPlBufferNowhere;
+  }
   auto fetch = [&](int r) {                         // row r of the walk; only rows -1 and h are ever reflected INTO a result,
     const int rm = 2 * h - 1 - r;                   // rows beyond (digested, never consumed) just need a valid address
     int rr = r < rm ? r : rm;
     rr = rr > 0 ? rr : 0;
     const char* row = reinterpret_cast<const char*>(f) + (size_t)rr * (size_t)w * 2u;   // scalar
     Raw x{uint4{0u, 0u, 0u, 0u}, 0};
-    if (load) {
+    if constexpr (BYOFFSET) {
+      const unsigned soff = (unsigned)rr * (unsigned)w * 2u;                            // scalar; < 2^31
+      x.q = pl_buffer_load_u128(rs, voffq, soff);
+      x.e = (int)pl_buffer_load_u16(rs, voffe, soff);                                   // its 16 bits: digest() extends them
+    } else if (load) {
       x.q = *reinterpret_cast<const uint4*>(row + offc);
       x.e = edge ? (int)*reinterpret_cast<const T*>(row + offe) : 0;
     }
@@ -49,6 +66,9 @@ __device__ __forceinline__ void pl_median3_rows(const T* __restrict__ f, int h, 
   int lo[3][8], mi[3][8], hi[3][8];
   auto digest = [&](const Raw& x, int slot) {
     const unsigned wd[4] = {x.q.x, x.q.y, x.q.z, x.q.w};
+    // BYOFFSET: the 2-byte load is extended HERE, at the row's turn (pl_extend16_here)
+    int xe = x.e;
+    if constexpr (BYOFFSET) xe = pl_extend16_here<T>(x.e);
     int v[10];   // columns c0-1 .. c0+8
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -56,8 +76,8 @@ __device__ __forceinline__ void pl_median3_rows(const T* __restrict__ f, int h, 
       v[2 + 2 * k] = (int)(T)(wd[k] >> 16);
     }
     // lane 0 / lane 63 have no neighbour in the wave: the DPP move leaves them `old` = the value loaded for them
-    const int left = __builtin_amdgcn_update_dpp(x.e, v[8], 0x138, 0xf, 0xf, false);    // wave_shr:1
-    const int right = __builtin_amdgcn_update_dpp(x.e, v[1], 0x130, 0xf, 0xf, false);   // wave_shl:1
+    const int left = __builtin_amdgcn_update_dpp(xe, v[8], 0x138, 0xf, 0xf, false);    // wave_shr:1
+    const int right = __builtin_amdgcn_update_dpp(xe, v[1], 0x130, 0xf, 0xf, false);   // wave_shl:1
     v[0] = first ? v[1] : left;     // reflect: column -1 -> column 0
     v[9] = last ? v[8] : right;     // column w -> column w-1
 #pragma unroll
@@ -118,3 +138,5 @@ __device__ __forceinline__ unsigned pl_pack16(int a, int b) { return ((unsigned)
 static inline bool pl_median3_rows_covers(const void* in, int h, int w) {
   return h > 1 && w >= 8 && (w & 7) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (((size_t)h * w) & 7) == 0;
 }
+// 1 when its BYOFFSET form does: the frame fits a bounded resource, with kPlBufferNowhere beyond it
+static inline bool pl_median3_rows_bounded_covers(int h, int w) { return (int64_t)h * (int64_t)w * 2 < (int64_t)kPlBufferNowhere; }

@@ -141,6 +141,37 @@ __device__ __forceinline__ void pl_buffer_store_u128(uint4 v, __amdgpu_buffer_rs
   typedef unsigned pl_v4u __attribute__((ext_vector_type(4)));
   __builtin_amdgcn_raw_buffer_store_b128(pl_v4u{v.x, v.y, v.z, v.w}, r, (int)lane_off, (int)uniform_off, 0);
 }
+// 16-byte and 2-byte loads (the 2-byte one zero-extended).  The CPU emulator of the tests knows the 4- and 8-byte loads only:
+// there the block is two halves and the half-word comes out of its aligned dword (a resource whose size is a multiple of 4
+// holds that dword whenever it holds the half-word)
+__device__ __forceinline__ uint4 pl_buffer_load_u128(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned uniform_off) {
+#ifdef PL_HIPEMU
+  const uint2 a = pl_buffer_load_u64(r, lane_off, uniform_off), b = pl_buffer_load_u64(r, lane_off + 8u, uniform_off);
+  return uint4{a.x, a.y, b.x, b.y};
+#else
+  const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)lane_off, (int)uniform_off, 0);
+  return uint4{(unsigned)v[0], (unsigned)v[1], (unsigned)v[2], (unsigned)v[3]};
+#endif
+}
+__device__ __forceinline__ unsigned pl_buffer_load_u16(__amdgpu_buffer_rsrc_t r, unsigned lane_off, unsigned uniform_off) {
+#ifdef PL_HIPEMU
+  const unsigned d = pl_buffer_load_u32(r, lane_off & ~3u, uniform_off);
+  return (lane_off & 2u) ? d >> 16 : d & 0xffffu;
+#else
+  return (unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, (int)lane_off, (int)uniform_off, 0);
+#endif
+}
+// The 16 bits of a pl_buffer_load_u16 that went through a ring of registers in a loop, extended to T's int at THIS place.
+// Left to the compiler, the extension of all the ring's slots becomes one group of operations at the loop's back edge, and
+// that group waits for every load in flight (s_waitcnt vmcnt(0)); the empty statement pins it to the value's consumer.
+template <typename T>
+__device__ __forceinline__ int pl_extend16_here(int v) {
+  unsigned short e = (unsigned short)v;
+  asm volatile("" : "+v"(e));
+  return (int)(T)e;
+}
+// a lane offset that no bounded resource holds (their sizes stay below 2^31): the access is dropped
+constexpr unsigned kPlBufferNowhere = 0x80000000u;
 
 // neighbour exchange inside a wave on the VALU's data-parallel path (DPP wave_shr:1 / wave_shl:1), NOT through the LDS
 // crossbar (__shfl_up / __shfl_down compile to ds_bpermute_b32, which queues behind a kernel's own LDS atomics).

@@ -154,6 +154,11 @@ threshold_colsum_kernel(const unsigned short* __restrict__ in, unsigned short* _
 constexpr int kMtRows = 32;                        // rows per wave: two halo rows are re-read per wave
 constexpr int kMtWaves = kBandRows / kMtRows;      // 4
 struct MtTile { size_t frame; int band, cg; };
+// The walk whose loads are predicated by offset (CELLS): rows in flight per lane, and the waves per SIMD its kernel is compiled
+// for (128 VGPRs, no scratch).  Measured on the bench frames and on a flood field at 4 / 6 / 8 rows and three / four waves
+// (DESIGN.md 5.4): four rows at four waves is the fastest on the bench frames that does not slow the flood field.
+constexpr int kMtAheadCells = 4;
+constexpr int kMtWavesPerSimdCells = 4;
 
 // The pixel work of one workgroup: thresholded medians stored, the four waves' column sums of the tile met in s_cs (complete
 // and visible to every lane on return); -> which tile of which frame this workgroup had.
@@ -203,14 +208,19 @@ __device__ __forceinline__ MtTile median3_threshold_tile(const unsigned short* _
   unsigned long long needed = ~0ull;                // the wave's lanes that need
   if (CELLS && rg < h) {
     const int cell_cols = (w + 63) / 64, row_groups = (h + kMtRows - 1) / kMtRows;
+    // a lane beyond the frame looks up the wave's first cell (lane 0 is always in the frame): no look-up under a branch
+    const size_t cell = (frame * row_groups + rg / kMtRows) * cell_cols + ((on ? c0 : cg * PL_WAVE * 8) >> 6);
+    const int cmax = cellmax[cell];
+    // KEEP: the entry is read next to the maximum, one wait for both; it counts in the cell's first lane and without `reset`
+    [[maybe_unused]] int entry = 0;
+    if constexpr (KEEP) entry = keep.zeroed[cell];
     // the same comparison as the pixel test m >= t: a cell whose maximum equals the threshold is needed
-    need = on && (int)cellmax[(frame * row_groups + rg / kMtRows) * cell_cols + (c0 >> 6)] >= t;
+    need = on && cmax >= t;
     needed = __ballot(need);
     load = (((needed << 1) | needed | (needed >> 1)) >> lane) & 1ull;
     if constexpr (KEEP) {
-      const size_t cell = (frame * row_groups + rg / kMtRows) * cell_cols + (c0 >> 6);
       const bool head = on && (lane & 7) == 0;
-      const bool was = head && !keep.reset && keep.zeroed[cell] != 0;
+      const bool was = head && !keep.reset && entry != 0;
       if (head && (keep.reset || was == need)) keep.zeroed[cell] = need ? 0 : 1;
       const unsigned long long kept = __ballot(was);          // bit 8 * cell: the cell's zeros are in `out` already
       store = on && (need || !((kept >> (lane & ~7)) & 1ull));
@@ -221,17 +231,36 @@ __device__ __forceinline__ MtTile median3_threshold_tile(const unsigned short* _
     if (KEEP ? store : on)
       for (int r = rg; r < r1; ++r) *reinterpret_cast<uint4*>(o + (size_t)r * w + c0) = uint4{0u, 0u, 0u, 0u};
   } else if (rg < h) {                              // wave-uniform
-    pl_median3_rows<unsigned short, kMtRows>(f, h, w, c0, lane, rg, [&](int r, const int (&m)[8]) {
-      if (KEEP ? !store : !on) return;
-      unsigned v[8];
+    if constexpr (CELLS) {
+      // `load` and `store` are run-time predicates here: both by OFFSET, not by branch (pl_median3_rows, BYOFFSET) -- the row's
+      // store is a buffer store on `out`'s frame that a lane which must not store aims beyond it, and nothing returns early, so
+      // the walk's loop is one block whose outstanding loads the compiler counts.  A lane that does not need adds zeros to its
+      // column sums (`need` implies `on`, a loading lane and loading neighbours), whatever it digested.
+      const __amdgpu_buffer_rsrc_t os = pl_make_rsrc_bounded(o, (unsigned)h * (unsigned)w * 2u);
+      const unsigned voff = store ? (unsigned)c0 * 2u : kPlBufferNowhere;
+      pl_median3_rows<unsigned short, kMtRows, kMtAheadCells, true>(f, h, w, c0, lane, rg, [&](int r, const int (&m)[8]) {
+        unsigned v[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        v[k] = (!CELLS || need) && m[k] >= t ? (unsigned)m[k] : 0u;
-        s[k] += v[k];
-      }
-      *reinterpret_cast<uint4*>(o + (size_t)r * w + c0) =
-          uint4{v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)};
-    }, load);
+        for (int k = 0; k < 8; ++k) {
+          v[k] = need && m[k] >= t ? (unsigned)m[k] : 0u;
+          s[k] += v[k];
+        }
+        pl_buffer_store_u128(uint4{v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)}, os, voff,
+                             (unsigned)r * (unsigned)w * 2u);
+      }, load);
+    } else {
+      pl_median3_rows<unsigned short, kMtRows>(f, h, w, c0, lane, rg, [&](int r, const int (&m)[8]) {
+        if (!on) return;
+        unsigned v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          v[k] = m[k] >= t ? (unsigned)m[k] : 0u;
+          s[k] += v[k];
+        }
+        *reinterpret_cast<uint4*>(o + (size_t)r * w + c0) =
+            uint4{v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16)};
+      });
+    }
 #pragma unroll
     for (int k = 0; k < 8; ++k) atomicAdd(&s_cs[lane * 8 + k], s[k]);     // 32 rows x 65535 per wave, 4 waves: < 2^32
   }
@@ -273,7 +302,7 @@ median3_threshold_colsum_kernel(const unsigned short* __restrict__ in, unsigned 
 // KEEP: and does not store again the zeros that `keep`'s table says are in `out` already.
 // (a pack of nothing, or of the one MtKeep<true>: without it the kernel's arguments are what they were)
 template <bool STAGE, bool CELLS, typename... KEEP>
-__global__ void __launch_bounds__(kMtWaves * PL_WAVE)
+__global__ void __launch_bounds__(kMtWaves * PL_WAVE) __attribute__((amdgpu_waves_per_eu(CELLS ? kMtWavesPerSimdCells : 1)))
 median3_threshold_tail_kernel(const unsigned short* __restrict__ in, unsigned short* __restrict__ out, int h, int w, int bands,
                               int col_groups, const int32_t* __restrict__ thr, const unsigned short* __restrict__ cellmax,
                               unsigned long long* __restrict__ ws,
@@ -509,7 +538,8 @@ extern "C" int pl_median3_threshold_colparts_u16(const uint16_t* in, uint16_t* o
 
 // smallest dynamic LDS of median3_threshold_tail_kernel's peak search that keeps the pass's three workgroups per CU (133 VGPRs:
 // three waves per SIMD; 3 x (48 KiB + 2.4 KiB of static LDS) < 160 KiB): the region staged in LDS if that fits, the candidate
-// tables alone otherwise; 0 = neither fits (regions beyond 3 000 samples)
+// tables alone otherwise; 0 = neither fits (regions beyond 3 000 samples).  (The CELLS instantiations are compiled for four
+// waves per SIMD; their fourth workgroup per CU fits where this is at most ~37 KiB, three run otherwise.)
 static size_t step_tail_lds(const pl_peak_params* params, int w, bool* stage_x, int* maxc) {
   const int lo = params->region_lo < 0 ? 0 : params->region_lo;
   const int hi = params->region_hi > w ? w : params->region_hi;
@@ -528,7 +558,7 @@ static size_t step_tail_lds(const pl_peak_params* params, int w, bool* stage_x, 
 extern "C" int pl_median3_threshold_profile_fwxm_covers(int h, int w, const pl_peak_params* params) {
   bool stage_x;
   int maxc;
-  return params && pl_median3_rows_covers(nullptr, h, w) && step_tail_lds(params, w, &stage_x, &maxc) != 0 ? 1 : 0;
+  return params && pl_median3_rows_covers(nullptr, h, w) && pl_median3_rows_bounded_covers(h, w) && step_tail_lds(params, w, &stage_x, &maxc) != 0 ? 1 : 0;
 }
 
 namespace {
@@ -551,6 +581,7 @@ int step_tail_launch(const char* who, const uint16_t* in, uint16_t* out, int64_t
   if (params->distance < 1) return bad("distance must be >= 1");
   if (!(pl_median3_rows_covers(in, h, w) && (reinterpret_cast<uintptr_t>(out) & 15) == 0))
     return bad("needs h > 1, width % 8 == 0 and 16-byte aligned frames (run the separate launches otherwise)");
+  if (CELLS && !pl_median3_rows_bounded_covers(h, w)) return bad("frames of 2^31 bytes or more (run the separate launches)");
   bool stage_x;
   int maxc;
   const size_t lds = step_tail_lds(params, w, &stage_x, &maxc);
