@@ -600,6 +600,45 @@ int pl_tiff_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* 
                    int64_t n_frames, int width, int height, int bits, int samples_per_pixel, int compressions, void* d_out,
                    int out_kind, int32_t* d_status, unsigned char* d_work, void* stream);
 
+/* ---- f1 ("next" row), the Deflate half: zlib.decompress, and PNG files -> typed frames --------------------------------
+ * pl_inflate replaces `zlib.decompress(data)` (wrapper 1: RFC 1950, CM = 8, CINFO <= 7, FCHECK valid, FDICT refused; the
+ * Adler-32 is NOT verified) and `zlib.decompress(data, -15)` (wrapper 0: raw RFC 1951) for n_streams streams lying anywhere
+ * inside one device buffer: stream i is the d_in_len[i] bytes at byte d_in_off[i] (int64, any alignment); its output goes to
+ * d_out + d_out_off[i], at most d_out_cap[i] bytes of it (the expected size: what lies beyond is never stored and a stream is
+ * complete once it has produced them); d_out_len[i] = the bytes written.  The caller owns d_out: every
+ * [d_out_off[i], d_out_off[i] + d_out_cap[i]) must lie inside it (output on a 16-byte boundary leaves in 16-byte stores).
+ * One wave per stream: stored, fixed and dynamic blocks, the last 32 KiB of output in an LDS ring.
+ *   d_status int32 [n_streams] (zeroed here): bit 0 the stream's window does not lie inside [0, nbytes) or d_out_cap[i] is
+ *   negative or above 2^31 - 1 (nothing stored), bit 1 the input ended first or the stream ended below d_out_cap[i] bytes,
+ *   bit 2 corrupt Deflate: a bad zlib header, block type 3, LEN != ~NLEN, an over-subscribed code set, an incomplete one
+ *   (other than no distance code at all or the single one-bit distance code RFC 1951 allows), no end-of-block code, HLIT
+ *   above 286 or HDIST above 30, literal/length symbol 286 / 287, distance symbol 30 / 31, a repeat code 16 with nothing to
+ *   repeat, a code-length run past HLIT + HDIST, a distance that reaches before the start of the output.
+ * pl_png_decode replaces `np.asarray(PIL.Image.open(f))` for a STACK of PNG files of one width, height, bit depth and colour
+ * type whose files lie anywhere inside one device buffer (copied as they are, compressed).  The host walks the chunks; the
+ * device sees IDAT payloads: segment s is the d_seg_len[s] bytes at byte d_seg_off[s] of frame d_seg_frame[s]; a frame's
+ * zlib stream is its segments in table order, which must be consecutive in the table.
+ *   bits / samples: 8 or 16 / 1 (grey) or 8 / 3 (RGB), else unsupported; non-interlaced, filter method 0 (types 0 - 4);
+ *   out_kind 0: d_out [n][height][width] in the container dtype (uint8, uint16 from big-endian samples; RGB: int32
+ *   (19595 R + 38470 G + 7471 B + 0x8000) >> 16, PIL's convert("I")), 1: uint16, 2: float64 (`array.astype(dtype)`);
+ *   d_status int32 [n] (zeroed here), per frame: bit 0 a segment descriptor is unsound (window outside [0, nbytes)) or the
+ *   frame's segments are not consecutive (such a frame is never read and NOTHING of it is stored), bits 1 and 2 as
+ *   pl_inflate's for the frame's stream against height x (1 + row bytes), bit 3 a filter-type byte above 4 (the row is taken
+ *   as unfiltered).  PIL raises OSError for each.  A flagged frame does not disturb the others.  Chunk CRCs are the host's
+ *   business (the Python reader does not verify them).
+ *   d_work: pl_png_work_bytes() bytes on a 16-byte boundary, idat_bytes >= the sum of the d_seg_len that lie inside the
+ *   buffer (-1 for arguments pl_png_decode refuses).
+ * Four launches whatever n is (check + scan, gather, inflate, unfilter + store); nothing is read back.  1 <= n <= 65535,
+ * n_segments >= 1, a frame with its filter bytes below 2 GiB, non-null pointers, d_bytes on a 4-byte boundary (else invalid
+ * argument): checked before any launch. */
+int pl_inflate(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_in_off, const int64_t* d_in_len,
+               int64_t n_streams, int wrapper, unsigned char* d_out, const int64_t* d_out_off, const int64_t* d_out_cap,
+               int64_t* d_out_len, int32_t* d_status, void* stream);
+int64_t pl_png_work_bytes(int64_t n, int64_t n_segments, int64_t idat_bytes, int width, int height, int bits, int samples);
+int pl_png_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_seg_off, const int64_t* d_seg_len,
+                  const int32_t* d_seg_frame, int64_t n_segments, int64_t n, int width, int height, int bits, int samples,
+                  void* d_out, int out_kind, int32_t* d_status, unsigned char* d_work, void* stream);
+
 /* ---- f2 ("next" row, first half): skimage.feature.canny as called at pylinac/planar_imaging.py:574-588 -------
  * float64 images, mask=None.  The caller composes: G = pl_gaussian2d_mode(mode 2) of the image and of an all-ones
  * frame; pl_canny_normalise: smoothed = G(image) / (G(ones) + eps); pl_sobel on axis 1 (jsobel) and axis 0 (isobel);
