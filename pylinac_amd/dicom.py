@@ -34,6 +34,7 @@ import torch
 
 from . import _lib
 from ._lib import PL_F32, PL_F64, PL_I16, PL_I32, PL_U8, PL_U16, check
+from ._stack_io import bytes_tensor, index_tensor, on_device
 from .geometry import Point
 
 MM_PER_INCH = 25.4
@@ -271,11 +272,10 @@ def decode_frames(file_bytes, offsets, rows: int, cols: int, bits_allocated: int
     in place) -> device tensor [N, rows, cols].  ``out``: "container" | "float32" | "float64"; ``rescale`` = (slope, intercept)
     with "float64".  Raises ``ValueError`` when a frame does not lie inside the buffer (pydicom: "The length of the pixel
     data in the dataset doesn't match the expected length")."""
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = on_device(device)
     buf = file_bytes if isinstance(file_bytes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(file_bytes, dtype=np.uint8))
     buf = buf.to(device=dev, dtype=torch.uint8).contiguous()
-    offs = (offsets.to(device=dev, dtype=torch.int64).contiguous() if isinstance(offsets, torch.Tensor)
-            else torch.as_tensor(np.asarray(offsets, dtype=np.int64)).to(dev))
+    offs = index_tensor(offsets, torch.int64, dev)
     n = int(offs.numel())
     rep = int(pixel_representation)
     cont = {(8, 0): torch.uint8, (8, 1): torch.int8, (16, 0): torch.uint16, (16, 1): torch.int16, (32, 0): torch.uint32,
@@ -293,12 +293,6 @@ def decode_frames(file_bytes, offsets, rows: int, cols: int, bits_allocated: int
     return res
 
 
-def _index(a, dev) -> torch.Tensor:
-    if isinstance(a, torch.Tensor):
-        return a.to(device=dev, dtype=torch.int64).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
-
-
 def decode_rle_frames(file_bytes, seg_off, seg_len, rows: int, cols: int, bits_allocated: int, bits_stored: int | None = None,
                       pixel_representation: int = 0, correct_unused_bits: bool = False, out: str = "container", rescale=None,
                       device=None, max_segment_bytes: int | None = None, native: torch.Tensor | None = None) -> torch.Tensor:
@@ -312,18 +306,16 @@ def decode_rle_frames(file_bytes, seg_off, seg_len, rows: int, cols: int, bits_a
     bytes, bit 2 to more (the frame is complete).  ``max_segment_bytes``: an upper bound of ``seg_len`` (taken from a host
     array when absent; a device tensor is reduced and read back once).  ``native``: a uint8 device tensor
     [N, rows * cols * BitsAllocated / 8] to decode into."""
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = on_device(device)
     bits, rep = int(bits_allocated), int(pixel_representation)
     cont = {(8, 0): torch.uint8, (8, 1): torch.int8, (16, 0): torch.uint16, (16, 1): torch.int16, (32, 0): torch.uint32,
             (32, 1): torch.int32}[(bits, rep)]
     segments = bits // 8
     if max_segment_bytes is None:
         max_segment_bytes = int(seg_len.max()) if isinstance(seg_len, torch.Tensor) else int(np.max(seg_len, initial=0))
-    if not isinstance(file_bytes, torch.Tensor):
-        held = np.ascontiguousarray(file_bytes, dtype=np.uint8)
-        file_bytes = torch.from_numpy(held if held.flags.writeable else held.copy())
-    buf = file_bytes.to(device=dev, dtype=torch.uint8).contiguous()
-    so, sl = _index(seg_off, dev).reshape(-1, segments), _index(seg_len, dev).reshape(-1, segments)
+    buf = bytes_tensor(file_bytes, dev)
+    so = index_tensor(seg_off, torch.int64, dev).reshape(-1, segments)
+    sl = index_tensor(seg_len, torch.int64, dev).reshape(-1, segments)
     n = int(so.shape[0])
     if so.shape != sl.shape:
         raise ValueError("decode_rle_frames: seg_off and seg_len must both be [N, BitsAllocated / 8]")

@@ -10,7 +10,6 @@ reference's ``FileImage`` hands its analyzers -- for grey files, and PIL's ``con
 """
 from __future__ import annotations
 
-import os
 import struct
 from dataclasses import dataclass, field
 from pathlib import Path
@@ -20,8 +19,8 @@ import torch
 
 from . import _lib
 from ._lib import check as _check
-from .tiff import _out_kind
-from .xim import _source_bytes
+from ._stack_io import (FileStack, bytes_tensor, file_name, frames_out, index_tensor, on_device, out_kind, pack_files,
+                        source_bytes, trim_frames)
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 STATUS_WINDOW, STATUS_SHORT, STATUS_CORRUPT_DEFLATE, STATUS_FILTER = 1, 2, 4, 8
@@ -63,7 +62,7 @@ def read_png(source, _what: str | None = None) -> PngInfo:
     their decode on the device), nor is the zlib stream's Adler-32.  Nothing about the pixel format is judged here
     (``load_frames`` refuses what the kernels do not decode)."""
     what = _what or (str(source) if isinstance(source, (str, Path)) else "PNG")
-    data = source if isinstance(source, (np.ndarray, memoryview)) else _source_bytes(source)
+    data = source if isinstance(source, (np.ndarray, memoryview)) else source_bytes(source)
     buf = memoryview(data).cast("B")
     n = len(buf)
     if n < 8 or bytes(buf[:8]) != SIGNATURE:
@@ -128,22 +127,12 @@ def _refuse(info: PngInfo, what: str):
         no("the IDAT chunks are not consecutive")
 
 
-def _device(device):
-    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-
-
-def _index(a, dt, npdt, dev):
-    if isinstance(a, torch.Tensor):
-        return a.to(device=dev, dtype=dt).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=npdt)).to(dev)
-
-
-def _bytes_tensor(buffer, dev):
-    if not isinstance(buffer, torch.Tensor):
-        host = np.ascontiguousarray(buffer, dtype=np.uint8)
-        buffer = torch.from_numpy(host if host.flags.writeable else host.copy())
-    buf = buffer.to(device=dev, dtype=torch.uint8).contiguous()
-    return buf if buf.numel() else torch.zeros(4, dtype=torch.uint8, device=dev)
+def _input(buffer, dev):
+    """-> (``buffer`` on the device, the size the kernel is told).  PNG's own, where the other loaders hand over the device
+    tensor and its ``numel()``: an empty buffer becomes 4 zero bytes, so that the kernel holds a pointer, while the size stays
+    that of the ARGUMENT, 0."""
+    buf = bytes_tensor(buffer, dev)
+    return (buf if buf.numel() else torch.zeros(4, dtype=torch.uint8, device=dev)), int(buf.numel())
 
 
 def inflate(buffer, in_off, in_len, out_cap, wrapper: bool = True, out_off=None, device=None, out=None):
@@ -154,8 +143,8 @@ def inflate(buffer, in_off, in_len, out_cap, wrapper: bool = True, out_off=None,
     on (default: one after the other on 16-byte boundaries; given offsets must keep every window inside ``out``).  status
     bits: 1 an unsound descriptor, 2 the input ended first or the stream ended below ``out_cap[i]``, 4 corrupt Deflate.  The
     Adler-32 is not verified."""
-    dev = _device(device)
-    buf = _bytes_tensor(buffer, dev)
+    dev = on_device(device)
+    buf, nbytes = _input(buffer, dev)
     caps = np.asarray(out_cap.cpu() if isinstance(out_cap, torch.Tensor) else out_cap, dtype=np.int64).reshape(-1)
     n = int(caps.size)
     if out_off is None:
@@ -167,15 +156,14 @@ def inflate(buffer, in_off, in_len, out_cap, wrapper: bool = True, out_off=None,
         out = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
     elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < need or (n and offs.min() < 0):
         raise ValueError("inflate: out must be a contiguous uint8 tensor that holds every [out_off, out_off + out_cap)")
-    off, ln = _index(in_off, torch.int64, np.int64, dev), _index(in_len, torch.int64, np.int64, dev)
+    off, ln = index_tensor(in_off, torch.int64, dev), index_tensor(in_len, torch.int64, dev)
     if off.dim() != 1 or int(off.numel()) != n or int(ln.numel()) != n or offs.size != n:
         raise ValueError("inflate: in_off / in_len / out_cap / out_off [S]")
     table = torch.from_numpy(np.concatenate([offs, caps])).to(dev)
     out_len = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
     status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    _check(_lib.load().pl_inflate(buf.data_ptr(), int(buffer.numel() if isinstance(buffer, torch.Tensor) else np.size(buffer)),
-                                  off.data_ptr(), ln.data_ptr(), n, 1 if wrapper else 0, out.data_ptr(), table[:n].data_ptr(),
-                                  table[n:].data_ptr(), out_len.data_ptr(), status.data_ptr(),
+    _check(_lib.load().pl_inflate(buf.data_ptr(), nbytes, off.data_ptr(), ln.data_ptr(), n, 1 if wrapper else 0, out.data_ptr(),
+                                  table[:n].data_ptr(), table[n:].data_ptr(), out_len.data_ptr(), status.data_ptr(),
                                   torch.cuda.current_stream(dev).cuda_stream), "pl_inflate")
     return out, table[:n], out_len[:n], status[:n]
 
@@ -188,96 +176,50 @@ def decode_png_streams(buffer, seg_off, seg_len, seg_frame, n: int, width: int, 
     ``idat_bytes`` (the sum of the lengths that lie inside the buffer) is derived from host arrays when not given.  ``out``:
     a device tensor to decode into.  status bits: 1 a segment outside the buffer or an unsound descriptor (nothing of the frame
     is stored), 2 the stream ends early, 4 corrupt Deflate, 8 a filter-type byte above 4."""
-    kind = _out_kind(dtype)
-    dev = _device(device)
-    buf = _bytes_tensor(buffer, dev)
-    nbytes = int(buffer.numel() if isinstance(buffer, torch.Tensor) else np.size(buffer))
+    kind = out_kind(dtype)
+    dev = on_device(device)
+    buf, nbytes = _input(buffer, dev)
     if idat_bytes is None:
         lens = np.asarray(seg_len.cpu() if isinstance(seg_len, torch.Tensor) else seg_len, dtype=np.int64)
         idat_bytes = int(np.clip(lens, 0, nbytes).sum())
-    off, ln = _index(seg_off, torch.int64, np.int64, dev), _index(seg_len, torch.int64, np.int64, dev)
-    frame = _index(seg_frame, torch.int32, np.int32, dev)
+    off, ln = index_tensor(seg_off, torch.int64, dev), index_tensor(seg_len, torch.int64, dev)
+    frame = index_tensor(seg_frame, torch.int32, dev)
     n_seg = int(off.numel())
     if off.dim() != 1 or int(ln.numel()) != n_seg or int(frame.numel()) != n_seg or frame.dim() != 1:
         raise ValueError("decode_png_streams: seg_off / seg_len / seg_frame [S]")
     lib = _lib.load()
     nwork = int(lib.pl_png_work_bytes(n, n_seg, idat_bytes, width, height, bits, samples))
     work = torch.empty(max(nwork, 16), dtype=torch.uint8, device=dev)
-    container = torch.int32 if samples == 3 else (torch.uint8 if bits == 8 else torch.uint16)
-    odt = (container, torch.uint16, torch.float64)[kind]
-    if out is None:
-        out = torch.empty((max(n, 1), height, width), dtype=odt, device=dev)
-    elif out.dtype != odt or out.numel() < n * height * width or not out.is_contiguous():
-        raise ValueError(f"decode_png_streams: out must be a contiguous {odt} tensor of N x height x width elements")
+    out = frames_out(out, "decode_png_streams", n, height, width, bits, samples, kind, dev)
     status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     _check(lib.pl_png_decode(buf.data_ptr(), nbytes, off.data_ptr(), ln.data_ptr(), frame.data_ptr(), n_seg, n, width, height,
                              bits, samples, out.data_ptr(), kind, status.data_ptr(), work.data_ptr(),
                              torch.cuda.current_stream(dev).cuda_stream), "pl_png_decode")
-    return out.reshape(-1)[:n * height * width].reshape(n, height, width), status[:n]
+    return trim_frames(out, n, height, width), status[:n]
 
 
-@dataclass
-class PngStack:
+class PngStack(FileStack):
     """What ``load_frames`` returns: ``frames`` [N, H, W] and ``status`` int32 [N] on the device, ``images`` the N files'
     ``PngInfo``; ``dpi`` the ``dpi=`` argument of the call (it overrides the files' pHYs chunks)."""
-    frames: torch.Tensor
-    status: torch.Tensor
-    images: list
-    dpi: float | None = None
-
-    @property
-    def dpmm(self) -> float | None:
-        """The files' common ``dpmm`` (``dpi / 25.4``; None when no file has a pHYs chunk in metres); ``ValueError`` when
-        they disagree."""
-        if self.dpi is not None:
-            return self.dpi / 25.4
-        values = [x.dpmm for x in self.images]
-        if any(v != values[0] for v in values[1:]):
-            raise ValueError("the PNG files of the stack differ in dpmm")
-        return values[0]
-
-
-def _name(images, k: int) -> str:
-    return f"file {k}" + (f" ({images[k].path})" if images[k].path is not None else "")
+    FORMAT = "PNG"
 
 
 def _stage(sources, device=None):
     """The host half of ``load_frames``: every file's chunks walked and judged, then the files laid at 4-byte boundaries of
     one pinned buffer and ONE copy of it queued -> (images, device buffer, segment offsets, lengths, frames, IDAT bytes)."""
-    sources = list(sources)
-    if not sources:
-        raise ValueError("load_frames: no files")
-    dev = _device(device)
-    held = [s if isinstance(s, (str, Path)) else _source_bytes(s) for s in sources]
-    sizes = [os.path.getsize(s) if isinstance(s, (str, Path)) else len(s) for s in held]
-    starts, pos = [], 0
-    for size in sizes:
-        starts.append(pos)
-        pos += (size + 3) & ~3
-    dbuf = torch.empty(pos, dtype=torch.uint8, device=dev)
-    host = torch.empty(pos, dtype=torch.uint8, pin_memory=dbuf.device.type == "cuda")
-    hv = host.numpy()
-    images = []
-    for k, (s, st, size) in enumerate(zip(held, starts, sizes)):
-        if isinstance(s, (str, Path)):
-            with open(s, "rb", buffering=0) as f:
-                got = f.readinto(memoryview(hv[st:st + size]))
-            if got != size:
-                raise OSError(f"{s}: read {got} of {size} bytes")
-        else:
-            hv[st:st + size] = np.frombuffer(s, dtype=np.uint8)
-        hv[st + size:st + ((size + 3) & ~3)] = 0
-        what = f"file {k}" + (f" ({s})" if isinstance(s, (str, Path)) else "")
-        info = read_png(hv[st:st + size], _what=f"load_frames: {what}")
-        info.path = s if isinstance(s, (str, Path)) else None
+    def parse(data, k, what):
+        info = read_png(data, _what=f"load_frames: {what}")
         _refuse(info, what)
-        images.append(info)
+        return info
+
+    images, starts, host, dbuf = pack_files(sources, device, parse)
+    dev = dbuf.device
     first = images[0]
     for k, x in enumerate(images):
         shape = (x.width, x.height, x.bits, x.colour_type)
         if shape != (first.width, first.height, first.bits, first.colour_type):
-            raise ValueError(f"load_frames: {_name(images, k)} differs from file 0 in width, height, bit depth or colour type: "
-                             f"{shape} against {(first.width, first.height, first.bits, first.colour_type)}")
+            raise ValueError(f"load_frames: {file_name(images, k)} differs from file 0 in width, height, bit depth or colour "
+                             f"type: {shape} against {(first.width, first.height, first.bits, first.colour_type)}")
     off, ln, frame = [], [], []
     for k, (st, x) in enumerate(zip(starts, images)):
         for o, c in x.idat:
@@ -301,7 +243,7 @@ def load_frames(sources, dtype=None, dpi=None, device=None, check: bool = True, 
     verified.  ``dpi`` overrides the files' pHYs chunks, as ``FileImage(path, dpi=...)`` does; ``out``: a device tensor to
     decode into.  ``check=True`` reads the status once and raises ``OSError`` naming the first flagged file (PIL raises
     ``OSError`` for truncated or corrupt image data); ``check=False`` transfers nothing back."""
-    _out_kind(dtype)                       # TypeError before any file is read
+    out_kind(dtype)                        # TypeError before any file is read
     images, dbuf, off, ln, frame, idat_bytes = _stage(sources, device)
     first = images[0]
     frames, status = decode_png_streams(dbuf, off, ln, frame, len(images), first.width, first.height, first.bits, first.samples,
@@ -314,5 +256,5 @@ def load_frames(sources, dtype=None, dpi=None, device=None, check: bool = True, 
                     "corrupt Deflate data" if got[k] & STATUS_CORRUPT_DEFLATE else
                     "the image data ends before the last row" if got[k] & STATUS_SHORT else
                     "a filter-type byte above 4")
-            raise OSError(f"load_frames: {_name(images, int(k))}: {what}")
+            raise OSError(f"load_frames: {file_name(images, int(k))}: {what}")
     return stack

@@ -10,7 +10,6 @@ for grey files, and PIL's ``convert("I")`` of an RGB file.
 """
 from __future__ import annotations
 
-import os
 import struct
 from dataclasses import dataclass, field
 from pathlib import Path
@@ -20,7 +19,8 @@ import torch
 
 from . import _lib
 from ._lib import check as _check
-from .xim import _source_bytes
+from ._stack_io import (FileStack, bytes_tensor, file_name, frames_out, index_tensor, on_device, out_kind, pack_files,
+                        source_bytes, trim_frames)
 
 COMPRESSION_NONE, COMPRESSION_LZW, COMPRESSION_PACKBITS = 1, 5, 32773
 _COMPRESSION_BIT = {COMPRESSION_NONE: 1, COMPRESSION_PACKBITS: 2, COMPRESSION_LZW: 4}
@@ -102,7 +102,7 @@ def read_tiff(source, _what: str | None = None) -> TiffInfo:
     at an offset, every offset validated against the file length.  Nothing about the pixel format is judged here
     (``load_frames`` refuses what the kernels do not decode)."""
     what = _what or (str(source) if isinstance(source, (str, Path)) else "TIFF")
-    data = source if isinstance(source, (np.ndarray, memoryview)) else _source_bytes(source)
+    data = source if isinstance(source, (np.ndarray, memoryview)) else source_bytes(source)
     order, tags = _walk_ifd(data, what)
     n = len(memoryview(data).cast("B"))
 
@@ -193,16 +193,6 @@ def _refuse(info: TiffInfo, data, what: str):
                 no(f"strip {k} is an old-style (bit-reversed) LZW stream, which is not supported")
 
 
-_OUT_KINDS = {None: 0, np.dtype(np.uint16): 1, np.dtype(np.float64): 2}
-
-
-def _out_kind(dtype) -> int:
-    try:
-        return _OUT_KINDS[None if dtype is None else np.dtype(dtype)]
-    except (KeyError, TypeError):
-        raise TypeError(f"dtype {dtype!r}: None (the container dtype), np.uint16 or np.float64") from None
-
-
 def decode_tiff_strips(buffer, strip_off, strip_len, strip_desc, frame_flags, width: int, height: int, bits: int,
                        samples: int = 1, dtype=None, device=None, compressions: int | None = None,
                        max_strip_bytes: int | None = None, out=None):
@@ -212,8 +202,8 @@ def decode_tiff_strips(buffer, strip_off, strip_len, strip_desc, frame_flags, wi
     2, bit 1 big-endian samples.  ``compressions`` (mask 1 none | 2 PackBits | 4 LZW) and ``max_strip_bytes`` are derived from
     host arrays when not given.  ``out``: a device tensor to decode into.  status bits: 1 a strip outside the buffer or an
     unsound descriptor (nothing of the frame is stored), 2 a short strip, 4 corrupt LZW."""
-    kind = _out_kind(dtype)
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    kind = out_kind(dtype)
+    dev = on_device(device)
     if compressions is None:
         compressions = 0
         for c in np.unique(np.asarray(strip_desc.cpu() if isinstance(strip_desc, torch.Tensor) else strip_desc)[:, 3]):
@@ -222,101 +212,47 @@ def decode_tiff_strips(buffer, strip_off, strip_len, strip_desc, frame_flags, wi
     if max_strip_bytes is None:
         max_strip_bytes = int(np.asarray(strip_len.cpu() if isinstance(strip_len, torch.Tensor) else strip_len).max(initial=0))
         max_strip_bytes = max(0, min(max_strip_bytes, 1 << 36))
-    if not isinstance(buffer, torch.Tensor):
-        host = np.ascontiguousarray(buffer, dtype=np.uint8)
-        buffer = torch.from_numpy(host if host.flags.writeable else host.copy())
-    buf = buffer.to(device=dev, dtype=torch.uint8).contiguous()
-
-    def index(a, dt, npdt):
-        if isinstance(a, torch.Tensor):
-            return a.to(device=dev, dtype=dt).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=npdt)).to(dev)
-
-    off, ln = index(strip_off, torch.int64, np.int64), index(strip_len, torch.int64, np.int64)
-    desc, flags = index(strip_desc, torch.int32, np.int32), index(frame_flags, torch.int32, np.int32)
+    buf = bytes_tensor(buffer, dev)
+    off, ln = index_tensor(strip_off, torch.int64, dev), index_tensor(strip_len, torch.int64, dev)
+    desc, flags = index_tensor(strip_desc, torch.int32, dev), index_tensor(frame_flags, torch.int32, dev)
     n_strips, n = int(off.numel()), int(flags.numel())
     if off.dim() != 1 or int(ln.numel()) != n_strips or tuple(desc.shape) != (n_strips, 4) or flags.dim() != 1:
         raise ValueError("decode_tiff_strips: strip_off / strip_len [S], strip_desc [S, 4], frame_flags [N]")
     lib = _lib.load()
     nwork = int(lib.pl_tiff_work_bytes(n, n_strips, max_strip_bytes, width, height, bits, samples, compressions))
     work = torch.empty(max(nwork, 16), dtype=torch.uint8, device=dev)
-    container = torch.int32 if samples == 3 else (torch.uint8 if bits == 8 else torch.uint16)
-    odt = (container, torch.uint16, torch.float64)[kind]
-    if out is None:
-        out = torch.empty((max(n, 1), height, width), dtype=odt, device=dev)
-    elif out.dtype != odt or out.numel() < n * height * width or not out.is_contiguous():
-        raise ValueError(f"decode_tiff_strips: out must be a contiguous {odt} tensor of N x height x width elements")
+    out = frames_out(out, "decode_tiff_strips", n, height, width, bits, samples, kind, dev)
     status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     _check(lib.pl_tiff_decode(buf.data_ptr(), buf.numel(), off.data_ptr(), ln.data_ptr(), desc.data_ptr(), n_strips,
                               max_strip_bytes, flags.data_ptr(), n, width, height, bits, samples, compressions, out.data_ptr(),
                               kind, status.data_ptr(), work.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
            "pl_tiff_decode")
-    return out.reshape(-1)[:n * height * width].reshape(n, height, width), status[:n]
+    return trim_frames(out, n, height, width), status[:n]
 
 
-@dataclass
-class TiffStack:
+class TiffStack(FileStack):
     """What ``load_frames`` returns: ``frames`` [N, H, W] and ``status`` int32 [N] on the device, ``images`` the N files'
     ``TiffInfo``; ``dpi`` the ``dpi=`` argument of the call (it overrides the files' resolution tags)."""
-    frames: torch.Tensor
-    status: torch.Tensor
-    images: list
-    dpi: float | None = None
-
-    @property
-    def dpmm(self) -> float | None:
-        """The files' common ``dpmm`` (``dpi / 25.4``; None when no file has resolution tags); ``ValueError`` when they
-        disagree."""
-        if self.dpi is not None:
-            return self.dpi / 25.4
-        values = [x.dpmm for x in self.images]
-        if any(v != values[0] for v in values[1:]):
-            raise ValueError("the TIFF files of the stack differ in dpmm")
-        return values[0]
-
-
-def _name(images, k: int) -> str:
-    return f"file {k}" + (f" ({images[k].path})" if images[k].path is not None else "")
+    FORMAT = "TIFF"
 
 
 def _stage(sources, device=None):
     """The host half of ``load_frames``: every file's IFD walked and judged, then the files laid at 4-byte boundaries of one
     pinned buffer and ONE copy of it queued -> (images, device buffer, strip offsets, lengths, descriptors, frame flags,
     compression mask, longest strip)."""
-    sources = list(sources)
-    if not sources:
-        raise ValueError("load_frames: no files")
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    held = [s if isinstance(s, (str, Path)) else _source_bytes(s) for s in sources]
-    sizes = [os.path.getsize(s) if isinstance(s, (str, Path)) else len(s) for s in held]
-    starts, pos = [], 0
-    for size in sizes:
-        starts.append(pos)
-        pos += (size + 3) & ~3
-    dbuf = torch.empty(pos, dtype=torch.uint8, device=dev)
-    host = torch.empty(pos, dtype=torch.uint8, pin_memory=dbuf.device.type == "cuda")
-    hv = host.numpy()
-    images = []
-    for k, (s, st, size) in enumerate(zip(held, starts, sizes)):
-        if isinstance(s, (str, Path)):
-            with open(s, "rb", buffering=0) as f:
-                got = f.readinto(memoryview(hv[st:st + size]))
-            if got != size:
-                raise OSError(f"{s}: read {got} of {size} bytes")
-        else:
-            hv[st:st + size] = np.frombuffer(s, dtype=np.uint8)
-        hv[st + size:st + ((size + 3) & ~3)] = 0
-        what = f"file {k}" + (f" ({s})" if isinstance(s, (str, Path)) else "")
-        info = read_tiff(hv[st:st + size], _what=what)
-        info.path = s if isinstance(s, (str, Path)) else None
-        _refuse(info, hv[st:st + size], what)
-        images.append(info)
+    def parse(data, k, what):
+        info = read_tiff(data, _what=what)
+        _refuse(info, data, what)
+        return info
+
+    images, starts, host, dbuf = pack_files(sources, device, parse)
+    dev = dbuf.device
     first = images[0]
     for k, x in enumerate(images):
         shape = (x.width, x.height, x.bits, x.samples)
         if shape != (first.width, first.height, first.bits, first.samples):
-            raise ValueError(f"load_frames: {_name(images, k)} differs from file 0 in width, height, bits per sample or samples "
-                             f"per pixel: {shape} against {(first.width, first.height, first.bits, first.samples)}")
+            raise ValueError(f"load_frames: {file_name(images, k)} differs from file 0 in width, height, bits per sample or "
+                             f"samples per pixel: {shape} against {(first.width, first.height, first.bits, first.samples)}")
     off, ln, desc, flags, mask = [], [], [], [], 0
     for k, (st, x) in enumerate(zip(starts, images)):
         flags.append((1 if x.predictor == 2 else 0) | (2 if x.byte_order == "MM" and x.bits == 16 else 0))
@@ -346,7 +282,7 @@ def load_frames(sources, dtype=None, dpi=None, device=None, check: bool = True) 
     the file before anything is copied.  ``dpi`` overrides the files' resolution tags, as ``FileImage(path, dpi=...)`` does.
     ``check=True`` reads the status once and raises ``OSError`` naming the first flagged file (PIL raises ``OSError`` for a
     truncated or corrupt strip); ``check=False`` transfers nothing back."""
-    _out_kind(dtype)                       # TypeError before any file is read
+    out_kind(dtype)                        # TypeError before any file is read
     images, dbuf, off, ln, desc, flags, mask, longest = _stage(sources, device)
     first = images[0]
     frames, status = decode_tiff_strips(dbuf, off, ln, desc, flags, first.width, first.height, first.bits, first.samples,
@@ -358,5 +294,5 @@ def load_frames(sources, dtype=None, dpi=None, device=None, check: bool = True) 
             what = ("a strip lies outside the file" if got[k] & STATUS_WINDOW else
                     "corrupt LZW data (a code names a table entry that does not exist)" if got[k] & STATUS_CORRUPT_LZW else
                     "a strip decodes to fewer bytes than its rows hold")
-            raise OSError(f"load_frames: {_name(images, int(k))}: {what}")
+            raise OSError(f"load_frames: {file_name(images, int(k))}: {what}")
     return stack

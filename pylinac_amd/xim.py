@@ -12,16 +12,15 @@ copy -> ONE ``pl_xim_decode_batch`` call (``decode_xim_batch``, the kernel-level
 """
 from __future__ import annotations
 
-import os
 import struct
 from dataclasses import dataclass
-from pathlib import Path
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import check
+from ._stack_io import bytes_tensor, file_name, index_tensor, on_device, out_kind, pack_files
 
 _DTYPES = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
 XIM_PROP_INT, XIM_PROP_DOUBLE, XIM_PROP_STRING, XIM_PROP_DOUBLE_ARRAY, XIM_PROP_INT_ARRAY = 0, 1, 2, 4, 5
@@ -35,9 +34,9 @@ def decode_xim_pixels(lookup_table_bytes, stream, width: int, height: int, bytes
     if bytes_per_pixel not in _DTYPES:
         raise ValueError("The XIM image has an unsupported bytes per pixel value. "
                          "Raise a ticket on the pylinac Github with this file.")
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = on_device(device)
 
-    def up(a):
+    def up(a):     # bytes_tensor without its copy of a read-only array: XIM(path) hands over views of the file's bytes
         t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8))
         return t.to(device=dev, dtype=torch.uint8).contiguous()
 
@@ -82,20 +81,6 @@ def _read(f, fmt: str, n: int = 1):
 
 def _read_str(f, n: int) -> str:
     return "".join(chr(b) for b in f.read(n) if b != 0)
-
-
-def _source_bytes(source) -> bytes:
-    """A path, a bytes-like object or a binary file object -> the file's bytes (what ``dicom.load_frames`` accepts)."""
-    if isinstance(source, (bytes, bytearray, memoryview)):
-        return bytes(source)
-    if isinstance(source, np.ndarray):
-        return source.tobytes()
-    if isinstance(source, (str, Path)):
-        with open(source, "rb") as f:
-            return f.read()
-    if hasattr(source, "seek"):
-        source.seek(0)
-    return source.read()
 
 
 def parse_xim(data, target, on_pixels=None):
@@ -173,7 +158,7 @@ class XIM:
                                 offset=buf_span[0])
             if lut_span is None:
                 dt = {1: np.int8, 2: np.int16, 4: np.int32, 8: np.int64}[self.bytes_per_pixel]
-                dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+                dev = on_device(device)
                 self.array = torch.from_numpy(raw.view(dt).reshape(self.img_height_px, self.img_width_px).copy()).to(dev)
             else:
                 self.array = decode_xim_pixels(self.lookup_table, raw, self.img_width_px, self.img_height_px,
@@ -189,15 +174,7 @@ class XIM:
         return 1 / (10 * self.properties["PixelHeight"])
 
 
-_OUT_KINDS = {None: 0, np.dtype(np.uint16): 1, np.dtype(np.float64): 2}
 _SHORT = "XIM pixel buffer is shorter than its lookup table implies"
-
-
-def _out_kind(dtype) -> int:
-    try:
-        return _OUT_KINDS[None if dtype is None else np.dtype(dtype)]
-    except (KeyError, TypeError):
-        raise TypeError(f"dtype {dtype!r}: None (the container dtype), np.uint16 or np.float64") from None
 
 
 def decode_xim_batch(buffer, lut_off, lut_len, buf_off, buf_len, width: int, height: int, bytes_per_pixel: int, dtype=None,
@@ -208,22 +185,13 @@ def decode_xim_batch(buffer, lut_off, lut_len, buf_off, buf_len, width: int, hei
     bytes).  -> (frames [N, height, width] in the container dtype, ``np.uint16`` or ``np.float64``; status int32 [N]), both
     on the device, nothing read back.  status bits: 1 a size code 3 (the reference's ``KeyError(3)``), 2 a lookup table or
     pixel buffer shorter than the shape implies or outside the buffer, 4 (uint16) a pixel outside 0 .. 65535."""
-    kind = _out_kind(dtype)
+    kind = out_kind(dtype)
     if bytes_per_pixel not in _DTYPES:
         raise ValueError("The XIM image has an unsupported bytes per pixel value. "
                          "Raise a ticket on the pylinac Github with this file.")
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    if not isinstance(buffer, torch.Tensor):
-        host = np.ascontiguousarray(buffer, dtype=np.uint8)
-        buffer = torch.from_numpy(host if host.flags.writeable else host.copy())
-    buf = buffer.to(device=dev, dtype=torch.uint8).contiguous()
-
-    def index(a):
-        if isinstance(a, torch.Tensor):
-            return a.to(device=dev, dtype=torch.int64).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
-
-    spans = [index(a) for a in (lut_off, lut_len, buf_off, buf_len)]
+    dev = on_device(device)
+    buf = bytes_tensor(buffer, dev)
+    spans = [index_tensor(a, torch.int64, dev) for a in (lut_off, lut_len, buf_off, buf_len)]
     n = int(spans[0].numel())
     if any(int(s.numel()) != n or s.dim() != 1 for s in spans):
         raise ValueError("decode_xim_batch: the four offset / length arrays must be 1-D and of one size")
@@ -260,55 +228,29 @@ def _stage(sources, device=None):
     """The host half of ``load_frames``: every file parsed, laid at a 4-byte boundary of one pinned buffer, ONE copy of that
     buffer queued -> (images, device buffer, int64 [4, N] device array of lookup offset / length and pixel-buffer offset /
     length inside it)."""
-    sources = list(sources)
-    if not sources:
-        raise ValueError("load_frames: no files")
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    # sizes first, so that the files are read straight into the pinned buffer and parsed where they lie
-    held = [s if isinstance(s, (str, Path)) else _source_bytes(s) for s in sources]
-    sizes = [os.path.getsize(s) if isinstance(s, (str, Path)) else len(s) for s in held]
-    starts, pos = [], 0
-    for size in sizes:
-        starts.append(pos)
-        pos += (size + 3) & ~3
-    dbuf = torch.empty(pos, dtype=torch.uint8, device=dev)
-    host = torch.empty(pos, dtype=torch.uint8, pin_memory=dbuf.device.type == "cuda")
-    hv = host.numpy()
-    images = []
-    for s, st, size in zip(held, starts, sizes):
-        if isinstance(s, (str, Path)):
-            with open(s, "rb", buffering=0) as f:
-                got = f.readinto(memoryview(hv[st:st + size]))
-            if got != size:
-                raise OSError(f"{s}: read {got} of {size} bytes")
-        else:
-            hv[st:st + size] = np.frombuffer(s, dtype=np.uint8)
-        hv[st + size:st + ((size + 3) & ~3)] = 0
+    def parse(data, k, what):
         x = XIM.__new__(XIM)
-        x.path = s if isinstance(s, (str, Path)) else None
-        x._spans = parse_xim(hv[st:st + size], x)
+        x._spans = parse_xim(data, x)
         if x.compression:
             x.lookup_table = x.lookup_table.copy()           # (not a view of the pinned buffer, which is handed back)
-        images.append(x)
+        return x
+
+    images, starts, host, dbuf = pack_files(sources, device, parse)
     first = images[0]
     for k, x in enumerate(images):
         if not x.compression:
-            raise ValueError(f"load_frames: {_name(images, k)} is not compressed; read it with XIM(path)")
+            raise ValueError(f"load_frames: {file_name(images, k)} is not compressed; read it with XIM(path)")
         if x.bytes_per_pixel not in _DTYPES:
             raise ValueError("The XIM image has an unsupported bytes per pixel value. "
                              "Raise a ticket on the pylinac Github with this file.")
         shape = (x.img_width_px, x.img_height_px, x.bytes_per_pixel)
         if shape != (first.img_width_px, first.img_height_px, first.bytes_per_pixel):
-            raise ValueError(f"load_frames: {_name(images, k)} differs from file 0 in width, height or bytes per pixel: "
+            raise ValueError(f"load_frames: {file_name(images, k)} differs from file 0 in width, height or bytes per pixel: "
                              f"{shape} against {(first.img_width_px, first.img_height_px, first.bytes_per_pixel)}")
     dbuf.copy_(host, non_blocking=True)
     spans = np.array([[st + x._spans[0][0], x._spans[0][1], st + x._spans[1][0], x._spans[1][1]]
                       for st, x in zip(starts, images)], dtype=np.int64).T
-    return images, dbuf, torch.from_numpy(np.ascontiguousarray(spans)).to(dev)
-
-
-def _name(images, k: int) -> str:
-    return f"file {k}" + (f" ({images[k].path})" if images[k].path is not None else "")
+    return images, dbuf, torch.from_numpy(np.ascontiguousarray(spans)).to(dbuf.device)
 
 
 def load_frames(sources, dtype=None, device=None, check: bool = True) -> XIMStack:
@@ -318,7 +260,7 @@ def load_frames(sources, dtype=None, device=None, check: bool = True) -> XIMStac
     lies and stores ``dtype`` (None: the container dtype, ``np.uint16`` or ``np.float64`` = ``array.astype(dtype)``).
     ``check=True`` reads the status once and raises for the first flagged file what ``XIM(path)`` raises (``KeyError(3)``,
     ``ValueError``), or a ``ValueError`` for a file that does not fit uint16; ``check=False`` transfers nothing back."""
-    _out_kind(dtype)                       # TypeError before any file is read
+    out_kind(dtype)                        # TypeError before any file is read
     images, dbuf, spans = _stage(sources, device)
     first = images[0]
     frames, status = decode_xim_batch(dbuf, spans[0], spans[1], spans[2], spans[3], first.img_width_px, first.img_height_px,
@@ -331,5 +273,5 @@ def load_frames(sources, dtype=None, device=None, check: bool = True) -> XIMStac
                 raise KeyError(3)      # the reference's LOOKUP_CONVERSION has no entry for size code 3
             if flags[k] & 2:
                 raise ValueError(_SHORT)
-            raise ValueError(f"load_frames: {_name(images, int(k))} holds pixels outside 0 .. 65535 and does not fit uint16")
+            raise ValueError(f"load_frames: {file_name(images, int(k))} holds pixels outside 0 .. 65535 and does not fit uint16")
     return stack

@@ -1,8 +1,7 @@
 """PNG files and Deflate streams (png.load_frames / decode_png_streams / pl_png_decode / pl_inflate) on the CPU emulator of
 tests/hipemu (kernel LOGIC where there is no GPU; the proof on hardware is tests/test_gpu_png.py): every case of
 tests/png_checks.py.  The emulator runs a fiber per work-item, so a file's output stays below about 100 KiB here; the
-512 x 512 and 1024 x 1024 frames and the hand-over to an analyzer run on the GPU only.  The emulated library is built from a
-fixed list of files; tests/png_emu.py builds png.hip beside it and hands out both."""
+512 x 512 and 1024 x 1024 frames and the hand-over to an analyzer run on the GPU only."""
 from __future__ import annotations
 
 import sys
@@ -20,7 +19,7 @@ import png_checks as checks  # noqa: E402
 
 @pytest.fixture(scope="module")
 def emulated():
-    from png_emu import emulated_device            # tests/emu_backend.py's context + png.hip built for the emulator
+    from emu_backend import emulated_device
 
     with emulated_device():
         yield torch.device("cuda:0")

@@ -1,6 +1,5 @@
 """starshot.wobble_batch / pl_starshot_wobble on the CPU emulator of tests/hipemu (kernel LOGIC where there is no GPU; the proof
-on hardware is tests/test_gpu_starshot_device.py): the cases of tests/starshot_device_checks.py.  The emulated library is built
-from a fixed list of files; tests/starshot_emu.py builds starshot.hip beside it and hands out both."""
+on hardware is tests/test_gpu_starshot_device.py): the cases of tests/starshot_device_checks.py."""
 from __future__ import annotations
 
 import sys
@@ -18,7 +17,7 @@ import starshot_device_checks as checks  # noqa: E402
 
 @pytest.fixture(scope="module")
 def emulated():
-    from starshot_emu import emulated_device       # tests/emu_backend.py's context + starshot.hip built for the emulator
+    from emu_backend import emulated_device
 
     with emulated_device():
         yield torch.device("cuda:0")

@@ -1,7 +1,6 @@
 """Strip TIFFs (tiff.load_frames / decode_tiff_strips / pl_tiff_decode) on the CPU emulator of tests/hipemu (kernel LOGIC where
 there is no GPU; the proof on hardware is tests/test_gpu_tiff.py): every case of tests/tiff_checks.py.  The emulator runs a
-fiber per work-item, so the 1024 x 1024 frames and the hand-over to an analyzer run on the GPU only.  The emulated library is
-built from a fixed list of files; tests/tiff_emu.py builds tiff.hip beside it and hands out both."""
+fiber per work-item, so the 1024 x 1024 frames and the hand-over to an analyzer run on the GPU only."""
 from __future__ import annotations
 
 import sys
@@ -19,7 +18,7 @@ import tiff_checks as checks  # noqa: E402
 
 @pytest.fixture(scope="module")
 def emulated():
-    from tiff_emu import emulated_device           # tests/emu_backend.py's context + tiff.hip built for the emulator
+    from emu_backend import emulated_device
 
     with emulated_device():
         yield torch.device("cuda:0")
