@@ -639,7 +639,39 @@ int pl_png_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d
                   const int32_t* d_seg_frame, int64_t n_segments, int64_t n, int width, int height, int bits, int samples,
                   void* d_out, int out_kind, int32_t* d_status, unsigned char* d_work, void* stream);
 
-/* ---- f2 ("next" row, first half): skimage.feature.canny as called at pylinac/planar_imaging.py:574-588 -------
+/* ---- f1 ("next" row), ZIP archives: zlib.crc32, and zipfile.ZipFile.read for every member of an archive ----------------
+ * pl_crc32 replaces `zlib.crc32(data)` for n_ranges byte ranges lying anywhere inside one device buffer: range i is the
+ * d_len[i] bytes at byte d_off[i] (int64, any alignment), max_len an upper bound of every length.
+ *   d_crc uint32 [n_ranges]; d_status int32 [n_ranges] (zeroed here): bit 0 the window does not lie inside [0, nbytes) or
+ *   the length exceeds max_len -- such a range is never read and d_crc[i] is left alone.  A range of length 0 gives 0.
+ *   d_work: pl_crc32_work_bytes() bytes on a 4-byte boundary (-1 for arguments pl_crc32 refuses): one word per tile of
+ *   16 KiB and range.  Two launches whatever n_ranges is (tiles, fold); nothing is read back.
+ *   1 <= n_ranges < 2^31, 0 <= max_len <= 65535 x 16384, non-null pointers, d_bytes on a 4-byte boundary (else invalid
+ *   argument): checked before any launch.
+ * pl_zip_extract replaces `[zf.read(name) for name in names]` for the members of a ZIP archive copied to the device as it
+ * is.  The host walks the central directory and the local headers; the device sees, per member, the d_in_len[m] bytes of
+ * its data at byte d_in_off[m], its method (0 stored, 8 Deflate), the CRC-32 and the size the central directory states;
+ * its bytes go to d_out + d_out_off[m] (d_out_size[m] of them; offsets on 16-byte boundaries let the inflate launch store
+ * 16 bytes at a time, any other offset works).
+ *   d_out_len int64 [n_members]: bytes stored per member.
+ *   d_status int32 [n_members], per member: bit 0 an unsound descriptor (a window outside [0, nbytes) or [0, out_bytes),
+ *   a size above max_size, a method other than 0 or 8, a stored member whose two sizes differ): NOTHING of that member is
+ *   stored; bits 1 and 2 as pl_inflate's against the member's size; bit 3 the CRC-32 of the stored bytes differs from
+ *   d_crc_expected[m] (verify = 1 only; not tested for a member already flagged).  A flagged member disturbs no other.
+ *   d_work: pl_zip_work_bytes() bytes on a 16-byte boundary (-1 for arguments pl_zip_extract refuses).
+ * At most five launches whatever n_members is (check, inflate, stored copy, the CRC pair over the output; three with
+ * verify = 0); nothing is read back.  1 <= n_members < 2^31, 0 <= max_size <= 65535 x 16384, non-null pointers, d_bytes
+ * and d_out on 4-byte boundaries (else invalid argument): checked before any launch. */
+int64_t pl_crc32_work_bytes(int64_t n_ranges, int64_t max_len);
+int pl_crc32(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_off, const int64_t* d_len,
+             int64_t n_ranges, int64_t max_len, uint32_t* d_crc, int32_t* d_status, unsigned char* d_work, void* stream);
+int64_t pl_zip_work_bytes(int64_t n_members, int64_t max_size);
+int pl_zip_extract(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_in_off, const int64_t* d_in_len,
+                   const int32_t* d_method, const uint32_t* d_crc_expected, int64_t n_members, int64_t max_size,
+                   unsigned char* d_out, int64_t out_bytes, const int64_t* d_out_off, const int64_t* d_out_size,
+                   int verify, int64_t* d_out_len, int32_t* d_status, unsigned char* d_work, void* stream);
+
+/* ---- f2("next" row, first half): skimage.feature.canny as called at pylinac/planar_imaging.py:574-588 -------
  * float64 images, mask=None.  The caller composes: G = pl_gaussian2d_mode(mode 2) of the image and of an all-ones
  * frame; pl_canny_normalise: smoothed = G(image) / (G(ones) + eps); pl_sobel on axis 1 (jsobel) and axis 0 (isobel);
  * pl_canny_nms: magnitude = hypot and the interpolated non-maximum suppression (uint8 local maxima);

@@ -180,7 +180,12 @@ SIGNATURES = {
     "pl_inflate": ([_p, _l, _p, _p, _l, _i, _p, _p, _p, _p, _p, _p], C.c_int),
     "pl_png_work_bytes": ([_l, _l, _l, _i, _i, _i, _i], C.c_int64),
     "pl_png_decode": ([_p, _l, _p, _p, _p, _l, _l, _i, _i, _i, _i, _p, _i, _p, _p, _p], C.c_int),
-    "pl_colsum_to_mean": ([_p, _l, _i, _i, _p, _p], C.c_int),
+    # zlib.crc32 / zipfile.ZipFile.read: byte ranges and the members of a ZIP archive (csrc/zip_kernels.h, part of png.hip)
+    "pl_crc32_work_bytes": ([_l, _l], C.c_int64),
+    "pl_crc32": ([_p, _l, _p, _p, _l, _l, _p, _p, _p, _p], C.c_int),
+    "pl_zip_work_bytes": ([_l, _l], C.c_int64),
+    "pl_zip_extract": ([_p, _l, _p, _p, _p, _p, _l, _l, _p, _l, _p, _p, _i, _p, _p, _p, _p], C.c_int),
+    "pl_colsum_to_mean":([_p, _l, _i, _i, _p, _p], C.c_int),
     "pl_find_peaks_var": (
         [_p, _l, _i, _p, _l, C.POINTER(PeakParams), _i, _p, _p, _p, _p, _p, _p, _p],
         C.c_int,

@@ -47,6 +47,9 @@
 // workgroup-scope release / acquire pair as in tiff_lzw_kernel.  A band takes chunks + 63 steps; every lane loads its next
 // chunk (aligned dwords, funnelled) one step ahead, and stores a chunk's samples in 16-byte pieces when the output rows are
 // 16-byte aligned (element stores otherwise, and for a row's last partial chunk).
+//
+// zip_kernels.h (included at the end: inflate_kernel is file-local) holds the other users of the Deflate half: CRC-32 of byte
+// ranges (pl_crc32) and the members of a ZIP archive (pl_zip_extract).
 #include "pl_common.h"
 
 namespace {
@@ -837,3 +840,5 @@ extern "C" int pl_png_decode(const unsigned char* d_bytes, int64_t nbytes, const
 #undef PN_FINISH
   return pl_check_launch("pl_png_decode");
 }
+
+#include "zip_kernels.h"

@@ -27,6 +27,7 @@ from __future__ import annotations
 import io
 import struct
 import warnings
+import zipfile
 from pathlib import Path
 
 import numpy as np
@@ -203,14 +204,37 @@ def read_part10(source) -> tuple[Metadata, np.ndarray]:
         if isinstance(source, io.IOBase) or hasattr(source, "seek"):
             source.seek(0)
         data = np.frombuffer(source.read(), dtype=np.uint8)
-    buf = memoryview(data).cast("B")
+    return _walk_part10(memoryview(data).cast("B")), data
+
+
+class _PrefixTooShort(Exception):
+    """the prefix of a member ends before its (7FE0,0010) element header"""
+
+
+def _walk_part10(buf: memoryview, size: int | None = None) -> Metadata:
+    """The element walk of ``read_part10`` over ``buf``.  ``size`` None: ``buf`` is the whole file.  Otherwise the PREFIX form
+    ``load_zip`` uses: ``buf`` holds the first bytes of a file of ``size`` bytes, the walk stops at the Pixel Data element
+    header -- (offset, length) of its value are validated against ``size``, not against the prefix -- and raises
+    ``_PrefixTooShort`` when the prefix ends before it (an element that is cut off is never read)."""
     n = len(buf)
+    whole = size is None or n >= size
+    try:
+        return _walk_elements(buf, n, size, whole)
+    except struct.error:
+        if whole:
+            raise
+        raise _PrefixTooShort from None
+
+
+def _walk_elements(buf: memoryview, n: int, size, whole: bool) -> Metadata:
     pos = 132 if n >= 132 and bytes(buf[128:132]) == b"DICM" else 0
     values: dict = {}
     ts = IMPLICIT_LE if pos == 0 else EXPLICIT_LE          # (no preamble, force=True: pydicom assumes implicit VR little endian)
     # the File Meta group is always explicit VR little endian (PS3.10 section 7.1)
     while pos + 8 <= n and struct.unpack_from("<H", buf, pos)[0] == 0x0002:
         pos, tag, vr, start, ln = _element(buf, pos, True, False)
+        if pos > n and not whole:
+            raise _PrefixTooShort
         if tag in _TAGS and ln >= 0:
             values[_TAGS[tag][0]] = _value(vr or _TAGS[tag][1], bytes(buf[start:start + ln]), False)
     ts = values.get("TransferSyntaxUID", ts)
@@ -220,9 +244,19 @@ def read_part10(source) -> tuple[Metadata, np.ndarray]:
         explicit, big = True, False                         # every encapsulated syntax is explicit VR little endian
     else:
         explicit, big = ts != IMPLICIT_LE, ts == EXPLICIT_BE
+    if size is not None and ts == RLE_LOSSLESS:
+        raise NotImplementedError("RLE Lossless Pixel Data inside an archive: the segment headers lie inside the compressed part; "
+                                  "extract the member and use load_frames")
     fragments = [] if ts == RLE_LOSSLESS else None
     while pos + 8 <= n:
         pos, tag, vr, start, ln = _element(buf, pos, explicit, big, fragments)
+        if size is not None and tag == (0x7FE0, 0x0010):    # the prefix form ends here: the value is judged against the file
+            if start > size or ln > size - start:
+                raise ValueError(f"the Pixel Data value ({ln} bytes at offset {start}) lies outside the file ({size} bytes)")
+            values["PixelData"] = (start, ln)
+            break
+        if pos > n and not whole:
+            raise _PrefixTooShort
         if tag == (0x7FE0, 0x0010) and ln < 0:
             values["PixelData"], values["PixelDataFragments"] = (start, -1), fragments
         if tag not in _TAGS or ln < 0:
@@ -232,8 +266,11 @@ def read_part10(source) -> tuple[Metadata, np.ndarray]:
             values[key] = (start, ln)
         else:
             values[key] = _value(vr if vr and vr != "UN" else table_vr, bytes(buf[start:start + ln]), big)
+    else:
+        if not whole:
+            raise _PrefixTooShort
     values.setdefault("TransferSyntaxUID", ts)
-    return Metadata(values), data
+    return Metadata(values)
 
 
 def _layout(meta: Metadata):
@@ -386,8 +423,6 @@ def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bo
     ``_rescale_dicom_values``;
     files with both rescale tags take the fused float64 form of the kernel when every file carries the SAME slope and
     intercept (a series), otherwise the frames are decoded once and rescaled file by file."""
-    from .image import rescale_dicom_values
-
     sources = list(sources)
     metas, blobs = [], []
     for s in sources:
@@ -454,6 +489,15 @@ def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bo
             return decode_frames(host, offsets, **common, **kw)
 
         verify = _check_status
+    return _finish_frames(decode, verify, metas, owner, rows, cols, dtype, raw_pixels, invert_pixels, check), metas
+
+
+def _finish_frames(decode, verify, metas, owner, rows: int, cols: int, dtype, raw_pixels: bool, invert_pixels, check: bool):
+    """The tail ``load_frames`` and ``load_zip`` share: ``decode(out=..., rescale=...)`` is the device decode of every frame,
+    ``verify(x)`` raises for a flagged one; the dtype rules, the rescale (fused when every file carries the same tags, file by
+    file otherwise) and the inversion of ``DicomImage.__init__``."""
+    from .image import rescale_dicom_values
+
     has_rescale = [("RescaleSlope" in m and "RescaleIntercept" in m) for m in metas]
     same = all(has_rescale) and len({(m.RescaleSlope, m.RescaleIntercept) for m in metas}) == 1
     inverts = [bool(invert_pixels or (invert_pixels is None and m.get("PixelIntensityRelationshipSign") == -1)) for m in metas]
@@ -501,7 +545,103 @@ def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bo
                 idx = np.flatnonzero(own == k)
                 a, b = int(idx[0]), int(idx[-1]) + 1
                 x[a:b] = ops.invert(x[a:b].reshape(1, (b - a) * rows, cols)).reshape(b - a, rows, cols)
-    return x, metas
+    return x
+
+
+def _member_header(raw, member, what: str):
+    """The Part-10 header of one archive member without inflating it whole -> its metadata, or None for a member without
+    ``DICM`` at byte 128.  ``raw``: the member's bytes as they lie in the archive (a uint8 array view).  A stored member is
+    walked where it lies; of a deflated one the first 64 KiB are inflated on the host, and twice as many again until the walk
+    reaches the (7FE0,0010) element header or the member ends."""
+    import zlib
+
+    if member.size < 132:
+        return None
+    if member.method == 0:
+        view = memoryview(raw).cast("B")
+        return _walk_part10(view, member.size) if bytes(view[128:132]) == b"DICM" else None
+    inflater, have, want, data = zlib.decompressobj(-15), bytearray(), 65536, memoryview(raw).cast("B")
+    while True:
+        try:
+            have += inflater.decompress(data, want - len(have))
+        except zlib.error as e:
+            raise zipfile.BadZipFile(f"{what}: corrupt Deflate data in its header ({e})") from None
+        data = inflater.unconsumed_tail
+        if len(have) >= 132 and bytes(have[128:132]) != b"DICM":
+            return None
+        ended = inflater.eof or (len(have) < want and not data)
+        try:
+            return _walk_part10(memoryview(have), len(have) if ended else max(member.size, len(have) + 1))
+        except _PrefixTooShort:
+            if ended:
+                raise zipfile.BadZipFile(f"{what}: the Deflate stream ends inside the data set's header") from None
+            want *= 2
+
+
+def load_zip(source, members=None, verify: bool = True, dtype=None, raw_pixels: bool = False, invert_pixels: bool | None = None,
+             correct_unused_bits: bool = False, device=None, check: bool = True):
+    """``load_frames([zf.read(n) for n in names], ...)`` for a ZIP archive of native Part-10 files (what
+    ``DicomImageStack.from_zip`` / ``CatPhan504.from_zip`` are handed) without a member ever being inflated whole on the host
+    -> (device tensor [N, H, W], list of per-member metadata, names).  The archive goes to the device compressed; ONE
+    ``pl_zip_extract`` (``zipstack.extract``) inflates every member with a wave of its own and, with ``verify``, checks its
+    CRC-32 as ``zipfile`` does; ``pl_dicom_decode`` then reads the frames where the members lie.  The host inflates only each
+    member's first kilobytes, for the Part-10 header walk.  ``members``: names in the order wanted; None takes every member
+    with ``DICM`` at byte 128, in central-directory order (``names`` lists them).  RLE Lossless members raise
+    ``NotImplementedError`` naming the member (their segment headers lie inside the compressed part); the other refusals, the
+    dtype rules, rescale and inversion are ``load_frames``'s own.  ``check=True`` reads the archive's status once
+    (``zipfile.BadZipFile``: ``Bad CRC-32 for file 'NAME'``) and the decode's.
+
+    The device form is for archives of MANY members of moderate size -- a CT volume: 80 - 300 slices of 0.5 MB, every Deflate
+    stream a wave of its own.  One Deflate stream is one serial chain (about 150 ns per output byte), so an archive of a few
+    large deflated members (a Winston-Lutz session of 1280 x 1280 frames) is read faster by ``zipfile`` on the host followed by
+    ``load_frames``; stored members cost a copy either way."""
+    from . import zipstack
+
+    archive, what, host, dbuf = zipstack.stage(source, device)
+    hv = host.numpy()
+    taken, metas = [], []
+    for m in zipstack._select(archive, members, what):
+        name = f"{what}: member {m.name!r}"
+        try:
+            meta = _member_header(hv[m.data_offset:m.data_offset + m.compressed_size], m, name)
+        except NotImplementedError as e:
+            raise NotImplementedError(f"{name}: {e}") from None
+        if meta is None:
+            if members is None:
+                continue
+            raise ValueError(f"{name}: not a DICOM Part-10 file (no DICM at byte 128)")
+        taken.append(m)
+        metas.append(meta)
+    if not taken:
+        raise ValueError(f"{what}: no DICOM members")
+    names = [m.name for m in taken]
+    lay = [_layout(m) for m in metas]
+    tdt, code, ib, _, rows, cols, big, _ = lay[0]
+    for l in lay[1:]:
+        if (l[0], l[4], l[5], l[6]) != (tdt, rows, cols, big):
+            raise ValueError("load_zip: the members differ in pixel format or frame size (the reference's stacks refuse that too)")
+    inside, owner = [], []                                  # frame offsets inside each member
+    for k, (m, l) in enumerate(zip(taken, lay)):
+        off, ln = l[7]
+        expected = l[3] * rows * cols * ib
+        if ln < expected:
+            raise ValueError(f"The length of the pixel data in the dataset ({ln} bytes) doesn't match the expected length "
+                             f"({expected} bytes). The dataset may be corrupted or there may be an issue with the pixel data handler.")
+        for f in range(l[3]):
+            inside.append(off + f * rows * cols * ib)
+            owner.append(k)
+    stack = zipstack.run(taken, what, host, dbuf, verify=verify, check=check)
+    offsets = stack.offsets[np.asarray(owner)] + np.asarray(inside, dtype=np.int64)
+    stored = int(metas[0].get("BitsStored") or ib * 8)
+    common = dict(rows=rows, cols=cols, bits_allocated=ib * 8, bits_stored=stored,
+                  pixel_representation=int(metas[0].PixelRepresentation), big_endian=big, correct_unused_bits=correct_unused_bits,
+                  device=stack.buffer.device)
+
+    def decode(**kw):
+        return decode_frames(stack.buffer, offsets, **common, **kw)
+
+    x = _finish_frames(decode, _check_status, metas, owner, rows, cols, dtype, raw_pixels, invert_pixels, check)
+    return x, metas, names
 
 
 def _astype(x: torch.Tensor, np_dt: np.dtype) -> torch.Tensor:
