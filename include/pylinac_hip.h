@@ -602,7 +602,7 @@ int pl_tiff_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* 
 
 /* ---- f1 ("next" row), the Deflate half: zlib.decompress, and PNG files -> typed frames --------------------------------
  * pl_inflate replaces `zlib.decompress(data)` (wrapper 1: RFC 1950, CM = 8, CINFO <= 7, FCHECK valid, FDICT refused; the
- * Adler-32 is NOT verified) and `zlib.decompress(data, -15)` (wrapper 0: raw RFC 1951) for n_streams streams lying anywhere
+ * Adler-32 is not verified HERE: pl_inflate_checked) and `zlib.decompress(data, -15)` (wrapper 0: raw RFC 1951) for n_streams streams lying anywhere
  * inside one device buffer: stream i is the d_in_len[i] bytes at byte d_in_off[i] (int64, any alignment); its output goes to
  * d_out + d_out_off[i], at most d_out_cap[i] bytes of it (the expected size: what lies beyond is never stored and a stream is
  * complete once it has produced them); d_out_len[i] = the bytes written.  The caller owns d_out: every
@@ -624,8 +624,8 @@ int pl_tiff_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* 
  *   d_status int32 [n] (zeroed here), per frame: bit 0 a segment descriptor is unsound (window outside [0, nbytes)) or the
  *   frame's segments are not consecutive (such a frame is never read and NOTHING of it is stored), bits 1 and 2 as
  *   pl_inflate's for the frame's stream against height x (1 + row bytes), bit 3 a filter-type byte above 4 (the row is taken
- *   as unfiltered).  PIL raises OSError for each.  A flagged frame does not disturb the others.  Chunk CRCs are the host's
- *   business (the Python reader does not verify them).
+ *   as unfiltered).  PIL raises OSError for each.  A flagged frame does not disturb the others.  Chunk CRCs and the
+ *   stream's Adler-32 are not verified here: pl_png_decode_checked.
  *   d_work: pl_png_work_bytes() bytes on a 16-byte boundary, idat_bytes >= the sum of the d_seg_len that lie inside the
  *   buffer (-1 for arguments pl_png_decode refuses).
  * Four launches whatever n is (check + scan, gather, inflate, unfilter + store); nothing is read back.  1 <= n <= 65535,
@@ -638,6 +638,61 @@ int64_t pl_png_work_bytes(int64_t n, int64_t n_segments, int64_t idat_bytes, int
 int pl_png_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_seg_off, const int64_t* d_seg_len,
                   const int32_t* d_seg_frame, int64_t n_segments, int64_t n, int width, int height, int bits, int samples,
                   void* d_out, int out_kind, int32_t* d_status, unsigned char* d_work, void* stream);
+
+/* ---- f1 ("next" row), checked Deflate: zlib.adler32, zlib.decompress with its data check, PNG files with their checksums ---
+ * pl_adler32 replaces `zlib.adler32(data)` for n_ranges byte ranges lying anywhere inside one device buffer, with the contract
+ * of pl_crc32 (below): range i is the d_len[i] bytes at byte d_off[i] (int64, any alignment), max_len an upper bound of every
+ * length.
+ *   d_adler uint32 [n_ranges]; d_status int32 [n_ranges] (zeroed here): bit 0 the window does not lie inside [0, nbytes) or
+ *   the length exceeds max_len -- such a range is never read and d_adler[i] is left alone.  A range of length 0 gives 1.
+ *   d_work: pl_adler32_work_bytes() bytes on an 8-byte boundary (-1 for arguments pl_adler32 refuses): two words per tile of
+ *   16 KiB and range.  Two launches whatever n_ranges is (tiles, fold); nothing is read back.
+ *   1 <= n_ranges < 2^31, 0 <= max_len <= 65535 x 16384, non-null pointers, d_bytes on a 4-byte boundary (else invalid
+ *   argument): checked before any launch.
+ * pl_inflate_checked is what `zlib.decompress(data)` really does, for zlib-wrapped streams (a raw stream has no trailer):
+ * pl_inflate's arguments with wrapper = 1, and besides max_out (an upper bound of every d_out_cap[i]), d_in_used and d_work.
+ * A stream is decoded on to the end-of-block code of its final block -- nothing beyond d_out_cap[i] is stored, and the wave
+ * gives up at the first byte beyond it --, the bits up to the next byte boundary are dropped, the four bytes there are the
+ * stream's Adler-32 (big-endian), and the Adler-32 of the bytes STORED is compared with them.  Bytes after the trailer are
+ * ignored, as zlib.decompress ignores them: d_in_used[i] = the bytes consumed, the trailer included
+ * (`decompressobj().unused_data` begins there; for a flagged stream: how far the decoder came).
+ *   d_status int32 [n_streams] (zeroed here): bits 0 - 2 as pl_inflate's (bit 0 also for d_out_cap[i] > max_out); bit 1 also
+ *   when the final block ended but fewer than 4 trailer bytes remain, and -- unlike pl_inflate -- when the input ends anywhere
+ *   before the final block does, whatever was produced (zlib: Error -5); bit 3 (8) the Adler-32 of the output differs from
+ *   the trailer (zlib: Error -3, incorrect data check; tested only when bits 0 - 2 and 4 are clear); bit 4 (16) the stream
+ *   produces more than d_out_cap[i] bytes: the first d_out_cap[i] are stored and the checksum is not judged.
+ *   d_work: pl_inflate_checked_work_bytes() bytes on a 16-byte boundary (-1 for arguments pl_inflate_checked refuses).
+ * Three launches whatever n_streams is (inflate, the Adler pair over the output); nothing is read back.  1 <= n_streams <
+ * 2^31, 0 <= max_out <= 65535 x 16384, non-null pointers, d_bytes and d_out on 4-byte boundaries (else invalid argument).
+ * pl_png_decode_checked is pl_png_decode with the file's checksums verified: the same arguments, then the chunk table --
+ * chunk c is the d_chunk_len[c] bytes (type + data) at byte d_chunk_off[c] of the buffer, its stored CRC-32 d_chunk_crc[c], its
+ * frame d_chunk_frame[c]; EVERY chunk of a file (IHDR, ancillary chunks, each IDAT, IEND); max_chunk_len an upper bound of the
+ * lengths -- and the stream.  Per frame, besides pl_png_decode's bits:
+ *   bit 4 (16) a chunk's CRC-32 differs from the stored one (or its window lies outside the buffer).  PIL verifies the chunks
+ *   in front of the pixel data and raises for them; it does NOT verify IDAT chunks, libpng does: this is libpng's rule;
+ *   bit 5 (32) the Adler-32 of the frame's inflated bytes differs from the stream's trailer (PIL: OSError, broken data
+ *   stream).  A stream that goes on beyond height x (1 + row bytes) is no error for a PNG (PIL stops reading there) and its
+ *   checksum is not judged; a stream whose trailer is cut sets bit 1.
+ *   A flagged frame disturbs no other, and its pixels are stored all the same: the caller decides.
+ *   d_work: pl_png_checked_work_bytes() bytes on a 16-byte boundary (-1 for arguments pl_png_decode_checked refuses; a frame
+ *   with its filter bytes is at most 65535 x 16384 bytes here).
+ * Nine launches whatever n is (pl_png_decode's four, the Adler pair after the inflate launch, the CRC pair over the chunks
+ * and their verdict); nothing is read back. */
+int64_t pl_adler32_work_bytes(int64_t n_ranges, int64_t max_len);
+int pl_adler32(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_off, const int64_t* d_len,
+               int64_t n_ranges, int64_t max_len, uint32_t* d_adler, int32_t* d_status, unsigned char* d_work, void* stream);
+int64_t pl_inflate_checked_work_bytes(int64_t n_streams, int64_t max_out);
+int pl_inflate_checked(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_in_off, const int64_t* d_in_len,
+                       int64_t n_streams, unsigned char* d_out, const int64_t* d_out_off, const int64_t* d_out_cap,
+                       int64_t max_out, int64_t* d_out_len, int64_t* d_in_used, int32_t* d_status,
+                       unsigned char* d_work, void* stream);
+int64_t pl_png_checked_work_bytes(int64_t n, int64_t n_segments, int64_t idat_bytes, int width, int height, int bits,
+                                  int samples, int64_t n_chunks, int64_t max_chunk_len);
+int pl_png_decode_checked(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_seg_off, const int64_t* d_seg_len,
+                          const int32_t* d_seg_frame, int64_t n_segments, int64_t n, int width, int height, int bits,
+                          int samples, void* d_out, int out_kind, int32_t* d_status, unsigned char* d_work,
+                          const int64_t* d_chunk_off, const int64_t* d_chunk_len, const uint32_t* d_chunk_crc,
+                          const int32_t* d_chunk_frame, int64_t n_chunks, int64_t max_chunk_len, void* stream);
 
 /* ---- f1 ("next" row), ZIP archives: zlib.crc32, and zipfile.ZipFile.read for every member of an archive ----------------
  * pl_crc32 replaces `zlib.crc32(data)` for n_ranges byte ranges lying anywhere inside one device buffer: range i is the

@@ -180,6 +180,13 @@ SIGNATURES = {
     "pl_inflate": ([_p, _l, _p, _p, _l, _i, _p, _p, _p, _p, _p, _p], C.c_int),
     "pl_png_work_bytes": ([_l, _l, _l, _i, _i, _i, _i], C.c_int64),
     "pl_png_decode": ([_p, _l, _p, _p, _p, _l, _l, _i, _i, _i, _i, _p, _i, _p, _p, _p], C.c_int),
+    # zlib.adler32 (csrc/adler32.hip), zlib.decompress with its data check, PNG files with their checksums (csrc/png.hip)
+    "pl_adler32_work_bytes": ([_l, _l], C.c_int64),
+    "pl_adler32": ([_p, _l, _p, _p, _l, _l, _p, _p, _p, _p], C.c_int),
+    "pl_inflate_checked_work_bytes": ([_l, _l], C.c_int64),
+    "pl_inflate_checked": ([_p, _l, _p, _p, _l, _p, _p, _p, _l, _p, _p, _p, _p, _p], C.c_int),
+    "pl_png_checked_work_bytes": ([_l, _l, _l, _i, _i, _i, _i, _l, _l], C.c_int64),
+    "pl_png_decode_checked": ([_p, _l, _p, _p, _p, _l, _l, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _l, _l, _p], C.c_int),
     # zlib.crc32 / zipfile.ZipFile.read: byte ranges and the members of a ZIP archive (csrc/zip_kernels.h, part of png.hip)
     "pl_crc32_work_bytes": ([_l, _l], C.c_int64),
     "pl_crc32": ([_p, _l, _p, _p, _l, _l, _p, _p, _p, _p], C.c_int),

@@ -42,6 +42,16 @@ void pl_packbits_expand(const unsigned char* d_bytes, int64_t nbytes, const int6
                         int64_t n_streams, int64_t max_stream_bytes, unsigned char* d_out, int32_t* d_status,
                         unsigned char* d_work, PlPackbitsGeom geom, hipStream_t st);
 
+// Adler-32 of byte ranges through adler32.hip's two launches (tiles, fold): range i is the d_len[i] bytes at d_off[i] of
+// d_bytes, each <= max_len; only dwords that hold a byte of a range are read.  d_gate: null, or one word per range -- a range
+// whose word is 0 is skipped (nothing read, nothing written).  d_adler: null, or where the checksums go.  d_expected: null, or
+// the checksum every range should have -- a mismatch ORs `mismatch` into d_status[i]; a window outside [0, nbytes) or longer
+// than max_len ORs 1.  d_slots: pl_adler32_slots_bytes() bytes on an 8-byte boundary (-1: n_ranges or max_len out of range).
+int64_t pl_adler32_slots_bytes(int64_t n_ranges, int64_t max_len);
+void pl_adler32_launch(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_off, const int64_t* d_len, int64_t n_ranges,
+                       int64_t max_len, const int32_t* d_gate, const uint32_t* d_expected, int mismatch, uint32_t* d_adler,
+                       int32_t* d_status, unsigned char* d_slots, hipStream_t st);
+
 // ---- device side -----------------------------------------------------------------------------
 // scipy 'reflect' (half-sample symmetric:  d c b a | a b c d | d c b a), valid for any distance.
 __device__ __forceinline__ int pl_reflect(int i, int n) {

@@ -48,9 +48,23 @@
 // chunk (aligned dwords, funnelled) one step ahead, and stores a chunk's samples in 16-byte pieces when the output rows are
 // 16-byte aligned (element stores otherwise, and for a row's last partial chunk).
 //
-// zip_kernels.h (included at the end: inflate_kernel is file-local) holds the other users of the Deflate half: CRC-32 of byte
+// zip_kernels.h (included near the end: inflate_kernel is file-local) holds the other users of the Deflate half: CRC-32 of byte
 // ranges (pl_crc32) and the members of a ZIP archive (pl_zip_extract).
+//
+// The checked mode (pl_inflate_checked, pl_png_decode_checked; the entry points follow zip_kernels.h, whose CRC launches the
+// second one uses).  inflate_kernel<true> decodes on to the end of the stream and leaves, per stream, the Adler-32 field it
+// found there and whether it is to be judged (PnChecked); the Adler pair of adler32.hip (pl_adler32_launch) then runs over what
+// was stored and compares.  pl_png_decode_checked adds pl_crc32's pair over every chunk of the files (type + data, against the
+// CRC the chunk stores) and png_chunk_verdict_kernel, which flags the chunk's frame: nine launches, whatever the stack.
+// inflate_kernel<false> is the kernel pl_inflate, pl_png_decode and pl_zip_extract launch, as before.
 #include "pl_common.h"
+
+// adler32.hip is a translation unit of its own in the library; the CPU emulator of the tests builds a fixed list of files
+// that holds this one, so there it is compiled as a part of this file
+#ifdef PL_HIPEMU
+#define PL_ADLER32_IN_PNG
+#include "adler32.hip"
+#endif
 
 namespace {
 
@@ -257,10 +271,23 @@ struct PnIn {                                               // the bit reader: a
   int64_t pos, win0;                                        // the next input byte to enter `buf`; the window's first byte
 };
 
+// CHECKED (pl_inflate_checked, pl_png_decode_checked): what the wave reports besides, per stream.  In that mode it does not
+// stop at out_cap bytes but decodes on to the end-of-block code of the BFINAL block -- storing nothing beyond out_cap, and
+// giving up at the first byte beyond it, which settles the verdict -- drops the bits up to the next byte boundary and reads the
+// four bytes there: the stream's Adler-32 field.
+struct PnChecked {
+  uint32_t* trailer;                                        // the Adler-32 field (big-endian in the stream)
+  int32_t* judge;                                           // 1: the stream ended at out_cap bytes with its field present: compare it
+  int64_t* in_used;                                         // null, or the bytes consumed, the field included
+  int64_t max_out;                                          // a capacity above it is an unsound descriptor
+  int overflow;                                             // ORed into the status of a stream that goes on beyond out_cap
+};
+
+template <bool CHECKED>
 __global__ void __launch_bounds__(PL_WAVE)
 inflate_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const int64_t* __restrict__ in_off,
                const int64_t* __restrict__ in_len, int wrapper, unsigned char* __restrict__ out, const int64_t* __restrict__ out_off,
-               const int64_t* __restrict__ out_cap, int64_t* __restrict__ out_len, int32_t* __restrict__ status) {
+               const int64_t* __restrict__ out_cap, int64_t* __restrict__ out_len, int32_t* __restrict__ status, PnChecked chk) {
   __shared__ uint4 s_ring4[kPnRing / 16];
   __shared__ unsigned s_in[kPnWindow / 4 + 4];
   __shared__ unsigned short s_lit[1 << kPnLitBits], s_dist[1 << kPnDistBits], s_cl[1 << kPnClBits];
@@ -272,14 +299,17 @@ inflate_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const in
   const int lane = threadIdx.x;
   if (status[s] & 1) return;                                // (pl_png_decode: a frame the check flagged)
   const int64_t off = in_off[s], len = in_len[s], cap64 = out_cap[s], dst0 = out_off[s];
-  if (!(off >= 0 && len >= 0 && off <= nbytes && len <= nbytes - off && cap64 >= 0 && cap64 < ((int64_t)1 << 31) && dst0 >= 0)) {
+  if (!(off >= 0 && len >= 0 && off <= nbytes && len <= nbytes - off && cap64 >= 0 && cap64 < ((int64_t)1 << 31) && dst0 >= 0) ||
+      (CHECKED && cap64 > chk.max_out)) {
     if (lane == 0) {
       atomicOr(status + s, 1);
       out_len[s] = 0;
+      if (CHECKED && chk.in_used) chk.in_used[s] = 0;
     }
     return;
   }
   const unsigned cap = (unsigned)cap64;
+  const unsigned lim = CHECKED ? cap + 1u : cap;            // where the token loops stop: one byte beyond out_cap tells enough
   unsigned char* dst = out + dst0;
   const bool aligned = ((uintptr_t)dst & 15u) == 0;
   const int64_t last_dword = ((nbytes < off + len ? nbytes : off + len) + 3) / 4 - 1;      // of the buffer, and of the stream
@@ -337,7 +367,7 @@ inflate_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const in
     else if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) flag = 4;
   }
   bool last = false;
-  while (!flag && !last && op < cap) {
+  while (!flag && !last && op < lim) {
     refill();
     last = take(1) != 0;
     const unsigned type = take(2);
@@ -366,9 +396,9 @@ inflate_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const in
       if ((int64_t)left > len - from) left = (unsigned)(len - from), flag = 2;   // the input ends inside the block
       in.buf = 0, in.nbits = 0, in.pos = from + left;
       const unsigned char* src = bytes + off;
-      while (left && op < cap) {
+      while (left && op < lim) {
         unsigned n = left < 1024u ? left : 1024u;
-        if (n > cap - op) n = cap - op;
+        if (n > lim - op) n = lim - op;
         for (unsigned k = lane; k < n; k += PL_WAVE) ring[(op + k) & (kPnRing - 1)] = src[from + k];
         op += n, from += n, left -= n;
         while (op - flushed >= (unsigned)kPnFlush) flush();
@@ -480,7 +510,7 @@ inflate_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const in
         // chain of code lengths is walked over the lanes' entries with v_readlane, and the lanes at which a literal begins
         // store their symbols together.  A code of the primary lookup lies wholly inside the kPnLitBits bits it was found by.
         const unsigned el = s_lit[(unsigned)(in.buf >> lane) & ((1u << kPnLitBits) - 1u)];
-        const unsigned room = cap - op;
+        const unsigned room = lim - op;
         unsigned long long starts = 0;
         int at = 0;
         unsigned n = 0;
@@ -498,7 +528,7 @@ inflate_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const in
               ring[(op + (unsigned)__popcll(starts & ((1ull << lane) - 1ull))) & (kPnRing - 1)] = (unsigned char)(el >> 4);
             op += n;
             in.buf = at < 64 ? in.buf >> at : 0ull, in.nbits -= at;
-            if (op >= cap) break;
+            if (op >= lim) break;
             continue;
           }
         }
@@ -517,7 +547,7 @@ inflate_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const in
         }
         if (lane == 0) ring[op & (kPnRing - 1)] = (unsigned char)sym;
         ++op;
-        if (op >= cap) break;
+        if (op >= lim) break;
         continue;
       }
       if (sym == 256) {
@@ -556,7 +586,7 @@ inflate_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const in
         flag = 4;
         break;
       }
-      if (n > cap - op) n = cap - op;
+      if (n > lim - op) n = lim - op;
       pl_wave_sync();
       // byte k of the match = byte k mod dist of the `dist` bytes before it (they lie wholly before the match: every lane
       // reads bytes that this token does not write; dist = 32768 and k names the slot the same lane is about to fill)
@@ -570,18 +600,47 @@ inflate_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const in
       }
       pl_wave_sync();
       op += n;
-      if (op >= cap) break;
+      if (op >= lim) break;
     }
   }
   // what is left in the ring
   pl_wave_sync();
   while (op - flushed >= (unsigned)kPnFlush) flush();
-  for (unsigned g = flushed + lane; g < op; g += PL_WAVE) dst[g] = ring[g & (kPnRing - 1)];
-  if (lane == 0) {
-    if (!flag && op < cap) flag = 2;                        // the stream ended below its expected size
-    if (op >= cap && flag == 2) flag = 0;                   // complete before the input ran out
-    if (flag) atomicOr(status + s, flag);
-    out_len[s] = op;
+  const unsigned stored = op < cap ? op : cap;
+  for (unsigned g = flushed + lane; g < stored; g += PL_WAVE) dst[g] = ring[g & (kPnRing - 1)];
+  if constexpr (!CHECKED) {
+    if (lane == 0) {
+      if (!flag && op < cap) flag = 2;                      // the stream ended below its expected size
+      if (op >= cap && flag == 2) flag = 0;                 // complete before the input ran out
+      if (flag) atomicOr(status + s, flag);
+      out_len[s] = op;
+    }
+  } else {
+    // the loop ended at the BFINAL block's end-of-block code (`last`, no flag, op <= cap), at a byte beyond out_cap, or with
+    // a flag.  Here the input running out is NOT forgiven by a full output: zlib reports an incomplete stream
+    const bool beyond = op > cap;
+    int64_t used = in.pos - (in.nbits >> 3);                // whole bytes consumed: the bits up to the byte boundary go
+    if (used > len) used = len;
+    unsigned field = 0;
+    int verdict = 0;
+    if (!flag && !beyond) {
+      if (op < cap) flag = 2;                               // the stream ended below its expected size
+      if (len - used < 4) {
+        flag |= 2, used = len;                              // the final block ended, the field is cut: zlib's Error -5
+      } else {
+        const unsigned char* t = bytes + off + used;
+        field = ((unsigned)t[0] << 24) | ((unsigned)t[1] << 16) | ((unsigned)t[2] << 8) | (unsigned)t[3];
+        used += 4;
+        verdict = flag == 0;
+      }
+    }
+    if (lane == 0) {
+      if (flag) atomicOr(status + s, flag);
+      if (beyond && !flag && chk.overflow) atomicOr(status + s, chk.overflow);
+      out_len[s] = stored;
+      chk.trailer[s] = field, chk.judge[s] = verdict;
+      if (chk.in_used) chk.in_used[s] = used;
+    }
   }
 }
 
@@ -763,6 +822,118 @@ __host__ bool pn_layout(int64_t n, int64_t n_segments, int64_t idat_bytes, int w
   return true;
 }
 
+// ---- the checked decode: chunk CRCs and the stream's Adler-32 (pl_png_decode_checked) ---------------------------------------
+// (zip_kernels.h, included at the end of this file)
+__host__ int64_t zp_crc_slots_bytes(int64_t n_ranges, int64_t max_len);
+__host__ void zp_crc_launch(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_off, const int64_t* d_len, int64_t n_ranges,
+                            int64_t max_len, const uint32_t* d_expected, uint32_t* d_crc, int32_t* d_status, unsigned char* d_slots,
+                            hipStream_t st);
+
+struct PnVerify {                                           // the chunk table, and where the checked mode's words live in d_work
+  const int64_t* chunk_off;
+  const int64_t* chunk_len;
+  const uint32_t* chunk_crc;
+  const int32_t* chunk_frame;
+  int64_t n_chunks, max_chunk_len;
+  int64_t trailer, judge, adler_slots, chunk_status, crc_slots;
+};
+
+// a chunk whose CRC-32 differs from the stored one (bit 3 of its own status, set by the CRC fold) or whose window lies outside
+// the buffer (bit 0) flags its frame
+__global__ void __launch_bounds__(kPnThreads)
+png_chunk_verdict_kernel(const int32_t* __restrict__ chunk_status, const int32_t* __restrict__ chunk_frame, int64_t n_chunks,
+                         int64_t n_frames, int32_t* __restrict__ status) {
+  const int64_t c = (int64_t)blockIdx.x * kPnThreads + threadIdx.x;
+  if (c >= n_chunks || chunk_status[c] == 0) return;
+  const int f = chunk_frame[c];
+  if (f >= 0 && f < n_frames) atomicOr(status + f, 16);
+}
+
+// the extra words lie where the plain layout has its compacted streams, which move behind them (they stay last)
+__host__ bool pn_checked_layout(int64_t n, int64_t n_segments, int64_t idat_bytes, int width, int height, int bits, int samples,
+                                int64_t n_chunks, int64_t max_chunk_len, PnLayout* lay, PnVerify* v) {
+  if (!pn_layout(n, n_segments, idat_bytes, width, height, bits, samples, lay)) return false;
+  const int64_t adler = pl_adler32_slots_bytes(n, lay->frame_bytes);
+  const int64_t crc = zp_crc_slots_bytes(n_chunks, max_chunk_len);
+  if (adler < 0 || crc < 0) return false;
+  auto up = [](int64_t x) { return (x + 15) & ~(int64_t)15; };
+  int64_t at = lay->compact;
+  v->trailer = at, at += up(n * 4);
+  v->judge = at, at += up(n * 4);                           // (zeroed together with the trailers)
+  v->adler_slots = at, at += adler;
+  v->chunk_status = at, at += up(n_chunks * 4);
+  v->crc_slots = at, at += crc;
+  lay->compact = at, at += up(idat_bytes) + 16;
+  lay->total = at;
+  v->n_chunks = n_chunks, v->max_chunk_len = max_chunk_len;
+  return true;
+}
+
+// the launches of pl_png_decode (v null: four) and of pl_png_decode_checked (nine: the Adler pair after the inflate launch,
+// the CRC pair and the chunks' verdict at the end)
+__host__ int pn_run(const char* who, const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_seg_off, const int64_t* d_seg_len,
+                    const int32_t* d_seg_frame, int64_t n_segments, int64_t n, int width, int height, int bits, int samples,
+                    void* d_out, int out_kind, int32_t* d_status, unsigned char* d_work, const PnLayout& lay, const PnVerify* v,
+                    hipStream_t st) {
+  bool zeroed = hipMemsetAsync(d_status, 0, (size_t)n * 4, st) == hipSuccess;
+  if (v) {
+    zeroed = zeroed && hipMemsetAsync(d_work + v->trailer, 0, (size_t)(v->adler_slots - v->trailer), st) == hipSuccess &&
+             hipMemsetAsync(d_work + v->chunk_status, 0, (size_t)v->n_chunks * 4, st) == hipSuccess;
+  }
+  if (!zeroed) {
+    pl_set_error("%s: memset failed", who);
+    return PL_ERR_HIP;
+  }
+  int64_t* seg_pos = reinterpret_cast<int64_t*>(d_work + lay.seg_pos);
+  int64_t* stream_off = reinterpret_cast<int64_t*>(d_work + lay.stream_off);
+  int64_t* stream_len = reinterpret_cast<int64_t*>(d_work + lay.stream_len);
+  int64_t* out_off = reinterpret_cast<int64_t*>(d_work + lay.out_off);
+  int64_t* out_cap = reinterpret_cast<int64_t*>(d_work + lay.out_cap);
+  int64_t* out_len = reinterpret_cast<int64_t*>(d_work + lay.out_len);
+  int32_t* head = reinterpret_cast<int32_t*>(d_work + lay.head);
+  unsigned char* compact = d_work + lay.compact;
+  unsigned char* inflated = d_work + lay.inflated;
+  hipLaunchKernelGGL(png_check_kernel, dim3(1), dim3(kPnThreads), 0, st, d_seg_off, d_seg_len, d_seg_frame, n_segments, nbytes, n,
+                     lay.frame_stride, lay.frame_bytes, seg_pos, head, stream_off, stream_len, out_off, out_cap, d_status);
+  hipLaunchKernelGGL(png_gather_kernel, dim3((unsigned)n_segments, 4), dim3(kPnThreads), 0, st, d_bytes, nbytes, d_seg_off, d_seg_len,
+                     d_seg_frame, n_segments, n, seg_pos, stream_off, stream_len, compact, d_status);
+  // (the streams were laid out by the check kernel inside the compacted area: its size is the caller's idat_bytes)
+  if (!v) {
+    hipLaunchKernelGGL(inflate_kernel<false>, dim3((unsigned)n), dim3(PL_WAVE), 0, st, compact, (int64_t)1 << 50, stream_off,
+                       stream_len, 1, inflated, out_off, out_cap, out_len, d_status, PnChecked{});
+  } else {
+    // a stream that goes on beyond the frame is no error for a PNG (PIL stops reading there): its checksum is not judged
+    uint32_t* trailer = reinterpret_cast<uint32_t*>(d_work + v->trailer);
+    int32_t* judge = reinterpret_cast<int32_t*>(d_work + v->judge);
+    hipLaunchKernelGGL(inflate_kernel<true>, dim3((unsigned)n), dim3(PL_WAVE), 0, st, compact, (int64_t)1 << 50, stream_off,
+                       stream_len, 1, inflated, out_off, out_cap, out_len, d_status,
+                       PnChecked{trailer, judge, nullptr, lay.frame_bytes, 0});
+    pl_adler32_launch(inflated, (int64_t)1 << 50, out_off, out_len, n, lay.frame_bytes, judge, trailer, 32, nullptr, d_status,
+                      d_work + v->adler_slots, st);
+  }
+  unsigned char* prev = d_work + lay.prev;
+#define PN_FINISH(BYTES, SPP, OUT)                                                                                          \
+  hipLaunchKernelGGL((png_unfilter_kernel<BYTES, SPP, OUT>), dim3((unsigned)n), dim3(PL_WAVE), 0, st, inflated, lay.frame_stride, \
+                     prev, lay.prev_stride, width, height, out_len, d_out, d_status)
+#define PN_OUT(BYTES, SPP)                         \
+  if (out_kind == 0) PN_FINISH(BYTES, SPP, 0);     \
+  else if (out_kind == 1) PN_FINISH(BYTES, SPP, 1); \
+  else PN_FINISH(BYTES, SPP, 2)
+  if (samples == 3) { PN_OUT(1, 3); }
+  else if (bits == 8) { PN_OUT(1, 1); }
+  else { PN_OUT(2, 1); }
+#undef PN_OUT
+#undef PN_FINISH
+  if (v) {
+    int32_t* chunk_status = reinterpret_cast<int32_t*>(d_work + v->chunk_status);
+    zp_crc_launch(d_bytes, nbytes, v->chunk_off, v->chunk_len, v->n_chunks, v->max_chunk_len, v->chunk_crc, nullptr, chunk_status,
+                  d_work + v->crc_slots, st);
+    hipLaunchKernelGGL(png_chunk_verdict_kernel, dim3((unsigned)pl_cdiv(v->n_chunks, kPnThreads)), dim3(kPnThreads), 0, st, chunk_status,
+                       v->chunk_frame, v->n_chunks, n, d_status);
+  }
+  return pl_check_launch(who);
+}
+
 }  // namespace
 
 extern "C" int pl_inflate(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_in_off, const int64_t* d_in_len,
@@ -778,8 +949,8 @@ extern "C" int pl_inflate(const unsigned char* d_bytes, int64_t nbytes, const in
     pl_set_error("pl_inflate: memset failed");
     return PL_ERR_HIP;
   }
-  hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)n_streams), dim3(PL_WAVE), 0, st, d_bytes, nbytes, d_in_off, d_in_len, wrapper,
-                     d_out, d_out_off, d_out_cap, d_out_len, d_status);
+  hipLaunchKernelGGL(inflate_kernel<false>, dim3((unsigned)n_streams), dim3(PL_WAVE), 0, st, d_bytes, nbytes, d_in_off, d_in_len,
+                     wrapper, d_out, d_out_off, d_out_cap, d_out_len, d_status, PnChecked{});
   return pl_check_launch("pl_inflate");
 }
 
@@ -804,41 +975,95 @@ extern "C" int pl_png_decode(const unsigned char* d_bytes, int64_t nbytes, const
   PnLayout lay;
   PL_REQUIRE(pn_layout(n, n_segments, 0, width, height, bits, samples, &lay),
              "1 <= n <= 65535, n_segments >= 1, width, height >= 1, a frame (with its filter bytes) below 2 GiB");
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(d_status, 0, (size_t)n * 4, st) != hipSuccess) {
-    pl_set_error("pl_png_decode: memset failed");
-    return PL_ERR_HIP;
-  }
-  int64_t* seg_pos = reinterpret_cast<int64_t*>(d_work + lay.seg_pos);
-  int64_t* stream_off = reinterpret_cast<int64_t*>(d_work + lay.stream_off);
-  int64_t* stream_len = reinterpret_cast<int64_t*>(d_work + lay.stream_len);
-  int64_t* out_off = reinterpret_cast<int64_t*>(d_work + lay.out_off);
-  int64_t* out_cap = reinterpret_cast<int64_t*>(d_work + lay.out_cap);
-  int64_t* out_len = reinterpret_cast<int64_t*>(d_work + lay.out_len);
-  int32_t* head = reinterpret_cast<int32_t*>(d_work + lay.head);
-  unsigned char* compact = d_work + lay.compact;
-  unsigned char* inflated = d_work + lay.inflated;
-  hipLaunchKernelGGL(png_check_kernel, dim3(1), dim3(kPnThreads), 0, st, d_seg_off, d_seg_len, d_seg_frame, n_segments, nbytes, n,
-                     lay.frame_stride, lay.frame_bytes, seg_pos, head, stream_off, stream_len, out_off, out_cap, d_status);
-  hipLaunchKernelGGL(png_gather_kernel, dim3((unsigned)n_segments, 4), dim3(kPnThreads), 0, st, d_bytes, nbytes, d_seg_off, d_seg_len,
-                     d_seg_frame, n_segments, n, seg_pos, stream_off, stream_len, compact, d_status);
-  // (the streams were laid out by the check kernel inside the compacted area: its size is the caller's idat_bytes)
-  hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)n), dim3(PL_WAVE), 0, st, compact, (int64_t)1 << 50, stream_off, stream_len, 1,
-                     inflated, out_off, out_cap, out_len, d_status);
-  unsigned char* prev = d_work + lay.prev;
-#define PN_FINISH(BYTES, SPP, OUT)                                                                                          \
-  hipLaunchKernelGGL((png_unfilter_kernel<BYTES, SPP, OUT>), dim3((unsigned)n), dim3(PL_WAVE), 0, st, inflated, lay.frame_stride, \
-                     prev, lay.prev_stride, width, height, out_len, d_out, d_status)
-#define PN_OUT(BYTES, SPP)                         \
-  if (out_kind == 0) PN_FINISH(BYTES, SPP, 0);     \
-  else if (out_kind == 1) PN_FINISH(BYTES, SPP, 1); \
-  else PN_FINISH(BYTES, SPP, 2)
-  if (samples == 3) { PN_OUT(1, 3); }
-  else if (bits == 8) { PN_OUT(1, 1); }
-  else { PN_OUT(2, 1); }
-#undef PN_OUT
-#undef PN_FINISH
-  return pl_check_launch("pl_png_decode");
+  return pn_run("pl_png_decode", d_bytes, nbytes, d_seg_off, d_seg_len, d_seg_frame, n_segments, n, width, height, bits, samples, d_out,
+                out_kind, d_status, d_work, lay, nullptr, (hipStream_t)stream);
 }
 
 #include "zip_kernels.h"
+
+// ---- the checked entry points (after zip_kernels.h: the chunk CRCs go through its launches) ---------------------------------
+namespace {
+
+struct PnInflateLayout {
+  int64_t trailer, judge, slots, total;
+};
+
+__host__ bool pn_inflate_layout(int64_t n, int64_t max_out, PnInflateLayout* lay) {
+  const int64_t slots = pl_adler32_slots_bytes(n, max_out);
+  if (slots < 0) return false;
+  auto up = [](int64_t v) { return (v + 15) & ~(int64_t)15; };
+  int64_t at = 0;
+  lay->trailer = at, at += up(n * 4);
+  lay->judge = at, at += up(n * 4);
+  lay->slots = at, at += slots;
+  lay->total = at;
+  return true;
+}
+
+}  // namespace
+
+extern "C" int64_t pl_inflate_checked_work_bytes(int64_t n_streams, int64_t max_out) {
+  PnInflateLayout lay;
+  return pn_inflate_layout(n_streams, max_out, &lay) ? lay.total : -1;
+}
+
+extern "C" int pl_inflate_checked(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_in_off, const int64_t* d_in_len,
+                                  int64_t n_streams, unsigned char* d_out, const int64_t* d_out_off, const int64_t* d_out_cap,
+                                  int64_t max_out, int64_t* d_out_len, int64_t* d_in_used, int32_t* d_status, unsigned char* d_work,
+                                  void* stream) {
+  PL_REQUIRE(d_bytes && d_in_off && d_in_len && d_out && d_out_off && d_out_cap && d_out_len && d_in_used && d_status && d_work,
+             "null pointer");
+  PL_REQUIRE(((uintptr_t)d_bytes & 3) == 0, "the byte buffer must start on a 4-byte boundary (streams inside it may start anywhere)");
+  PL_REQUIRE(((uintptr_t)d_out & 3) == 0, "d_out must start on a 4-byte boundary");
+  PL_REQUIRE(((uintptr_t)d_work & 15) == 0, "d_work must start on a 16-byte boundary");
+  PL_REQUIRE(nbytes >= 0, "bad buffer size");
+  PnInflateLayout lay;
+  PL_REQUIRE(pn_inflate_layout(n_streams, max_out, &lay), "1 <= n_streams < 2^31, 0 <= max_out <= 65535 x 16 KiB");
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(d_status, 0, (size_t)n_streams * 4, st) != hipSuccess ||
+      hipMemsetAsync(d_work, 0, (size_t)lay.slots, st) != hipSuccess) {
+    pl_set_error("pl_inflate_checked: memset failed");
+    return PL_ERR_HIP;
+  }
+  uint32_t* trailer = reinterpret_cast<uint32_t*>(d_work + lay.trailer);
+  int32_t* judge = reinterpret_cast<int32_t*>(d_work + lay.judge);
+  hipLaunchKernelGGL(inflate_kernel<true>, dim3((unsigned)n_streams), dim3(PL_WAVE), 0, st, d_bytes, nbytes, d_in_off, d_in_len, 1,
+                     d_out, d_out_off, d_out_cap, d_out_len, d_status, PnChecked{trailer, judge, d_in_used, max_out, 16});
+  // the checksum of what was STORED, for the streams that ended where they should (the caller owns d_out: its size is unknown
+  // here, and the Adler kernels read no dword outside a range)
+  pl_adler32_launch(d_out, (int64_t)1 << 50, d_out_off, d_out_len, n_streams, max_out, judge, trailer, 8, nullptr, d_status,
+                    d_work + lay.slots, st);
+  return pl_check_launch("pl_inflate_checked");
+}
+
+extern "C" int64_t pl_png_checked_work_bytes(int64_t n, int64_t n_segments, int64_t idat_bytes, int width, int height, int bits,
+                                             int samples, int64_t n_chunks, int64_t max_chunk_len) {
+  PnLayout lay;
+  PnVerify v;
+  return pn_checked_layout(n, n_segments, idat_bytes, width, height, bits, samples, n_chunks, max_chunk_len, &lay, &v) ? lay.total : -1;
+}
+
+extern "C" int pl_png_decode_checked(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_seg_off, const int64_t* d_seg_len,
+                                     const int32_t* d_seg_frame, int64_t n_segments, int64_t n, int width, int height, int bits,
+                                     int samples, void* d_out, int out_kind, int32_t* d_status, unsigned char* d_work,
+                                     const int64_t* d_chunk_off, const int64_t* d_chunk_len, const uint32_t* d_chunk_crc,
+                                     const int32_t* d_chunk_frame, int64_t n_chunks, int64_t max_chunk_len, void* stream) {
+  if (!((samples == 1 && (bits == 8 || bits == 16)) || (samples == 3 && bits == 8))) {
+    pl_set_error("pl_png_decode_checked: unsupported samples (%d x %d bits): grey of 8 or 16 bits, RGB of 8", samples, bits);
+    return PL_ERR_UNSUPPORTED;
+  }
+  PL_REQUIRE(d_bytes && d_seg_off && d_seg_len && d_seg_frame && d_out && d_status && d_work, "null pointer");
+  PL_REQUIRE(d_chunk_off && d_chunk_len && d_chunk_crc && d_chunk_frame, "null pointer (the chunk table)");
+  PL_REQUIRE(((uintptr_t)d_bytes & 3) == 0, "the byte buffer must start on a 4-byte boundary (segments inside it may start anywhere)");
+  PL_REQUIRE(((uintptr_t)d_work & 15) == 0, "d_work must start on a 16-byte boundary");
+  PL_REQUIRE(out_kind >= 0 && out_kind <= 2, "out_kind 0 (container dtype), 1 (uint16) or 2 (float64)");
+  PL_REQUIRE(nbytes >= 0 && nbytes <= ((int64_t)1 << 40), "bad buffer size");
+  PnLayout lay;
+  PnVerify v;
+  PL_REQUIRE(pn_checked_layout(n, n_segments, 0, width, height, bits, samples, n_chunks, max_chunk_len, &lay, &v),
+             "1 <= n <= 65535, n_segments >= 1, width, height >= 1, a frame (with its filter bytes) of at most 65535 x 16 KiB, "
+             "1 <= n_chunks < 2^31, 0 <= max_chunk_len <= 65535 x 16 KiB");
+  v.chunk_off = d_chunk_off, v.chunk_len = d_chunk_len, v.chunk_crc = d_chunk_crc, v.chunk_frame = d_chunk_frame;
+  return pn_run("pl_png_decode_checked", d_bytes, nbytes, d_seg_off, d_seg_len, d_seg_frame, n_segments, n, width, height, bits,
+                samples, d_out, out_kind, d_status, d_work, lay, &v, (hipStream_t)stream);
+}

@@ -365,8 +365,8 @@ extern "C" int pl_zip_extract(const unsigned char* d_bytes, int64_t nbytes, cons
   int64_t* inf_cap = reinterpret_cast<int64_t*>(d_work + lay.inf_cap);
   hipLaunchKernelGGL(zip_check_kernel, dim3((unsigned)pl_cdiv(n_members, kZpThreads)), dim3(kZpThreads), 0, st, d_in_off, d_in_len,
                      d_method, d_out_off, d_out_size, n_members, nbytes, out_bytes, max_size, inf_off, inf_len, inf_cap, d_status);
-  hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)n_members), dim3(PL_WAVE), 0, st, d_bytes, nbytes, inf_off, inf_len, 0, d_out,
-                     d_out_off, inf_cap, d_out_len, d_status);
+  hipLaunchKernelGGL(inflate_kernel<false>, dim3((unsigned)n_members), dim3(PL_WAVE), 0, st, d_bytes, nbytes, inf_off, inf_len, 0,
+                     d_out, d_out_off, inf_cap, d_out_len, d_status, PnChecked{});
   int64_t pieces = pl_cdiv(max_size, (int64_t)kZpThreads * 4 * 16);
   pieces = pieces < 1 ? 1 : (pieces > 64 ? 64 : pieces);
   hipLaunchKernelGGL(zip_stored_kernel, dim3((unsigned)n_members, (unsigned)pieces), dim3(kZpThreads), 0, st, d_bytes, nbytes, d_in_off,

@@ -2,7 +2,7 @@
 export or a Winston-Lutz session as one ``.zip``): the directory walk on the host, Deflate and the CRC-32 on the device.
 
 ``read_zip`` walks the End Of Central Directory record, the central directory and the local headers -> ``ZipMember`` records;
-``crc32`` is ``zlib.crc32`` for a batch of byte ranges (``pl_crc32``); ``extract`` is ``[zf.read(n) for n in names]``: the
+``crc32`` / ``adler32`` are ``zlib.crc32`` / ``zlib.adler32`` for a batch of byte ranges (``pl_crc32``, ``pl_adler32``); ``extract`` is ``[zf.read(n) for n in names]``: the
 archive, still compressed, into one pinned buffer -> one copy -> ONE ``pl_zip_extract`` call (raw Deflate streams inflated
 one wave each, stored members copied, the CRC-32 of every member's OUTPUT compared with the directory's) -> ``ZipStack`` with
 the members' bytes in one device buffer and a per-member status, nothing read back unless ``check``.
@@ -111,12 +111,8 @@ def read_zip(source, _what: str | None = None) -> list:
     return members
 
 
-def crc32(buffer, offsets, lengths, device=None, out=None):
-    """``pl_crc32``: ``zlib.crc32`` of R byte ranges lying anywhere inside ``buffer`` (uint8 array / tensor; a device tensor
-    is used in place) -> (crc uint32 [R], status int32 [R]), both on the device, nothing read back.  Range i is the
-    ``lengths[i]`` bytes at byte ``offsets[i]``.  status bit 1: the window does not lie inside the buffer -- that range's crc
-    word is not written (``out``: a uint32 device tensor [R] to write into; default: zeros).  An upper bound of the lengths is
-    taken from a host array; a device tensor is reduced and read back once."""
+def _checksum(which: str, buffer, offsets, lengths, device, out):
+    """``pl_crc32`` / ``pl_adler32``: the two share their contract line for line"""
     dev = on_device(device)
     buf = bytes_tensor(buffer, dev)
     nbytes = int(buf.numel())
@@ -127,20 +123,35 @@ def crc32(buffer, offsets, lengths, device=None, out=None):
     off, ln = index_tensor(offsets, torch.int64, dev), index_tensor(lengths, torch.int64, dev)
     n = int(off.numel())
     if off.dim() != 1 or ln.dim() != 1 or int(ln.numel()) != n:
-        raise ValueError("crc32: offsets / lengths [R]")
+        raise ValueError(f"{which}: offsets / lengths [R]")
     lib = _lib.load()
-    nwork = int(lib.pl_crc32_work_bytes(n, max_len))
+    nwork = int(getattr(lib, f"pl_{which}_work_bytes")(n, max_len))
     work = torch.empty(max(nwork, 16), dtype=torch.uint8, device=dev)
     if out is None:
-        crc = torch.zeros(max(n, 1), dtype=torch.uint32, device=dev)
+        value = torch.zeros(max(n, 1), dtype=torch.uint32, device=dev)
     elif out.dtype != torch.uint32 or not out.is_contiguous() or out.numel() < n:
-        raise ValueError("crc32: out must be a contiguous uint32 tensor [R]")
+        raise ValueError(f"{which}: out must be a contiguous uint32 tensor [R]")
     else:
-        crc = out
+        value = out
     status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    _check(lib.pl_crc32(buf.data_ptr(), nbytes, off.data_ptr(), ln.data_ptr(), n, max_len, crc.data_ptr(), status.data_ptr(),
-                        work.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "pl_crc32")
-    return crc[:n], status[:n]
+    _check(getattr(lib, f"pl_{which}")(buf.data_ptr(), nbytes, off.data_ptr(), ln.data_ptr(), n, max_len, value.data_ptr(),
+                                       status.data_ptr(), work.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), f"pl_{which}")
+    return value[:n], status[:n]
+
+
+def crc32(buffer, offsets, lengths, device=None, out=None):
+    """``pl_crc32``: ``zlib.crc32`` of R byte ranges lying anywhere inside ``buffer`` (uint8 array / tensor; a device tensor
+    is used in place) -> (crc uint32 [R], status int32 [R]), both on the device, nothing read back.  Range i is the
+    ``lengths[i]`` bytes at byte ``offsets[i]``.  status bit 1: the window does not lie inside the buffer -- that range's crc
+    word is not written (``out``: a uint32 device tensor [R] to write into; default: zeros).  An upper bound of the lengths is
+    taken from a host array; a device tensor is reduced and read back once."""
+    return _checksum("crc32", buffer, offsets, lengths, device, out)
+
+
+def adler32(buffer, offsets, lengths, device=None, out=None):
+    """``pl_adler32``: ``zlib.adler32`` of R byte ranges lying anywhere inside ``buffer`` -> (adler uint32 [R], status int32
+    [R]), both on the device, nothing read back: the arguments, the status and ``out`` of ``crc32``.  An empty range gives 1."""
+    return _checksum("adler32", buffer, offsets, lengths, device, out)
 
 
 def extract_members(buffer, in_off, in_len, method, crc_expected, out_off, out_size, verify: bool = True, device=None, out=None):
