@@ -599,6 +599,25 @@ int pl_tiff_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* 
                    const int32_t* d_strip_desc, int64_t n_strips, int64_t max_strip_bytes, const int32_t* d_frame_flags,
                    int64_t n_frames, int width, int height, int bits, int samples_per_pixel, int compressions, void* d_out,
                    int out_kind, int32_t* d_status, unsigned char* d_work, void* stream);
+/* The same two with Deflate strips: `compressions` may also carry bit 8 (masks 1 .. 15) for strips whose Compression is 8
+ * (Adobe Deflate) or 32946 (the older code; one codec in libtiff), each ONE zlib stream (RFC 1950).  Everything above holds;
+ * pl_tiff_decode and pl_tiff_work_bytes go on refusing masks above 7.  A Deflate strip is inflated by one wave straight into
+ * its rows (pl_inflate's kernel in its checked mode) and is always checked, as libtiff hands zlib the whole strip:
+ *   d_status, further bits per frame: bit 1 (value 2) also for a Deflate strip whose input ended, or whose stream ended, below
+ *   rows x row bytes; bit 3 (value 8) corrupt Deflate data in a strip -- an invalid block type, code set or distance, a stored
+ *   block whose length check fails, a zlib header that is not CM 8 / CINFO <= 7 / FCHECK-valid or that sets FDICT, a raw
+ *   stream without the header (PIL: OSError); bit 4 (value 16) a strip's stream ended at rows x row bytes and the Adler-32
+ *   field behind it differs from the checksum of what was stored (PIL: OSError, "incorrect data check").
+ *   Not errors, as in libtiff: bytes after the stream's end, an Adler-32 field that is cut off (the strip is complete before
+ *   it), a stream that goes on beyond rows x row bytes (the rest is dropped, its checksum not judged).
+ * With bit 8 five launches are added (at most twelve) and a frame may hold at most 65535 x 16 KiB; d_work:
+ * pl_tiff_work_bytes_ex() bytes. */
+int64_t pl_tiff_work_bytes_ex(int64_t n_frames, int64_t n_strips, int64_t max_strip_bytes, int width, int height, int bits,
+                              int samples_per_pixel, int compressions);
+int pl_tiff_decode_ex(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_strip_off, const int64_t* d_strip_len,
+                      const int32_t* d_strip_desc, int64_t n_strips, int64_t max_strip_bytes, const int32_t* d_frame_flags,
+                      int64_t n_frames, int width, int height, int bits, int samples_per_pixel, int compressions, void* d_out,
+                      int out_kind, int32_t* d_status, unsigned char* d_work, void* stream);
 
 /* ---- f1 ("next" row), the Deflate half: zlib.decompress, and PNG files -> typed frames --------------------------------
  * pl_inflate replaces `zlib.decompress(data)` (wrapper 1: RFC 1950, CM = 8, CINFO <= 7, FCHECK valid, FDICT refused; the

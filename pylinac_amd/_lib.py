@@ -176,6 +176,8 @@ SIGNATURES = {
     "pl_dicom_rle_decode": ([_p, _l, _p, _p, _l, _i, _l, _i, _i, _p, _p, _p, _p], C.c_int),
     "pl_tiff_work_bytes": ([_l, _l, _l, _i, _i, _i, _i, _i], C.c_int64),
     "pl_tiff_decode": ([_p, _l, _p, _p, _p, _l, _l, _p, _l, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p], C.c_int),
+    "pl_tiff_work_bytes_ex": ([_l, _l, _l, _i, _i, _i, _i, _i], C.c_int64),
+    "pl_tiff_decode_ex": ([_p, _l, _p, _p, _p, _l, _l, _p, _l, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p], C.c_int),
     # zlib.decompress / np.asarray(PIL.Image.open(png)): Deflate streams and stacks of PNG files (csrc/png.hip)
     "pl_inflate": ([_p, _l, _p, _p, _l, _i, _p, _p, _p, _p, _p, _p], C.c_int),
     "pl_png_work_bytes": ([_l, _l, _l, _i, _i, _i, _i], C.c_int64),

@@ -52,6 +52,23 @@ void pl_adler32_launch(const unsigned char* d_bytes, int64_t nbytes, const int64
                        int64_t max_len, const int32_t* d_gate, const uint32_t* d_expected, int mismatch, uint32_t* d_adler,
                        int32_t* d_status, unsigned char* d_slots, hipStream_t st);
 
+// Deflate streams through png.hip's inflate_kernel, one wave per stream (tiff.hip's Deflate strips; pl_inflate,
+// pl_inflate_checked and the PNG decoders launch it this way too).  Stream i is the d_in_len[i] bytes at d_in_off[i] of d_bytes
+// (wrapper 1: a zlib stream, 0: raw Deflate); at most d_out_cap[i] bytes of it go to d_out + d_out_off[i], d_out_len[i] = the
+// bytes stored.  d_status[i]: a stream whose word has bit 0 set on entry is left alone (nothing read, nothing written, its
+// d_out_len / trailer / judge words included); bit 0 an unsound window, bit 1 the input ended first or the stream ended
+// below d_out_cap[i], bit 2 corrupt Deflate.  `checked`: decode on to the end of the stream and report what PnChecked names.
+struct PnChecked {
+  uint32_t* trailer;                                        // the Adler-32 field (big-endian in the stream)
+  int32_t* judge;                                           // 1: the stream ended at out_cap bytes with its field present: compare it
+  int64_t* in_used;                                         // null, or the bytes consumed, the field included
+  int64_t max_out;                                          // a capacity above it is an unsound descriptor
+  int overflow;                                             // ORed into the status of a stream that goes on beyond out_cap
+};
+void pl_inflate_launch(bool checked, const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_in_off, const int64_t* d_in_len,
+                       int64_t n_streams, int wrapper, unsigned char* d_out, const int64_t* d_out_off, const int64_t* d_out_cap,
+                       int64_t* d_out_len, int32_t* d_status, PnChecked chk, hipStream_t st);
+
 // ---- device side -----------------------------------------------------------------------------
 // scipy 'reflect' (half-sample symmetric:  d c b a | a b c d | d c b a), valid for any distance.
 __device__ __forceinline__ int pl_reflect(int i, int n) {

@@ -34,7 +34,8 @@
 //            wave inside the ring (byte k of the match is byte k mod distance of the source, which lies wholly before the
 //            match: byte-serial semantics for overlapping matches, distance 1 included), a stored block is copied by the wave
 //            from the staged input's memory into the ring.  Whenever 4 KiB are complete they leave for global memory in 16-byte
-//            pieces (64 lanes x 4); nothing the wave stored to global memory is ever read back, so there is no release /
+//            pieces (64 lanes x 4; byte stores when the destination is not on a 16-byte boundary, as for tiff.hip's Deflate
+//            strips of odd row_bytes); nothing the wave stored to global memory is ever read back, so there is no release /
 //            acquire pair in this kernel.  Output beyond out_cap is never stored.
 // status per stream: bit 0 unsound descriptor, bit 1 the input ended first or the stream ended below out_cap, bit 2 corrupt
 // Deflate (see include/pylinac_hip.h for the list).
@@ -271,18 +272,10 @@ struct PnIn {                                               // the bit reader: a
   int64_t pos, win0;                                        // the next input byte to enter `buf`; the window's first byte
 };
 
-// CHECKED (pl_inflate_checked, pl_png_decode_checked): what the wave reports besides, per stream.  In that mode it does not
-// stop at out_cap bytes but decodes on to the end-of-block code of the BFINAL block -- storing nothing beyond out_cap, and
-// giving up at the first byte beyond it, which settles the verdict -- drops the bits up to the next byte boundary and reads the
-// four bytes there: the stream's Adler-32 field.
-struct PnChecked {
-  uint32_t* trailer;                                        // the Adler-32 field (big-endian in the stream)
-  int32_t* judge;                                           // 1: the stream ended at out_cap bytes with its field present: compare it
-  int64_t* in_used;                                         // null, or the bytes consumed, the field included
-  int64_t max_out;                                          // a capacity above it is an unsound descriptor
-  int overflow;                                             // ORed into the status of a stream that goes on beyond out_cap
-};
-
+// CHECKED (pl_inflate_checked, pl_png_decode_checked, tiff.hip's Deflate strips): what the wave reports besides, per stream
+// (PnChecked, pl_common.h).  In that mode it does not stop at out_cap bytes but decodes on to the end-of-block code of the
+// BFINAL block -- storing nothing beyond out_cap, and giving up at the first byte beyond it, which settles the verdict -- drops
+// the bits up to the next byte boundary and reads the four bytes there: the stream's Adler-32 field.
 template <bool CHECKED>
 __global__ void __launch_bounds__(PL_WAVE)
 inflate_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const int64_t* __restrict__ in_off,
@@ -899,15 +892,14 @@ __host__ int pn_run(const char* who, const unsigned char* d_bytes, int64_t nbyte
                      d_seg_frame, n_segments, n, seg_pos, stream_off, stream_len, compact, d_status);
   // (the streams were laid out by the check kernel inside the compacted area: its size is the caller's idat_bytes)
   if (!v) {
-    hipLaunchKernelGGL(inflate_kernel<false>, dim3((unsigned)n), dim3(PL_WAVE), 0, st, compact, (int64_t)1 << 50, stream_off,
-                       stream_len, 1, inflated, out_off, out_cap, out_len, d_status, PnChecked{});
+    pl_inflate_launch(false, compact, (int64_t)1 << 50, stream_off, stream_len, n, 1, inflated, out_off, out_cap, out_len, d_status,
+                      PnChecked{}, st);
   } else {
     // a stream that goes on beyond the frame is no error for a PNG (PIL stops reading there): its checksum is not judged
     uint32_t* trailer = reinterpret_cast<uint32_t*>(d_work + v->trailer);
     int32_t* judge = reinterpret_cast<int32_t*>(d_work + v->judge);
-    hipLaunchKernelGGL(inflate_kernel<true>, dim3((unsigned)n), dim3(PL_WAVE), 0, st, compact, (int64_t)1 << 50, stream_off,
-                       stream_len, 1, inflated, out_off, out_cap, out_len, d_status,
-                       PnChecked{trailer, judge, nullptr, lay.frame_bytes, 0});
+    pl_inflate_launch(true, compact, (int64_t)1 << 50, stream_off, stream_len, n, 1, inflated, out_off, out_cap, out_len, d_status,
+                      PnChecked{trailer, judge, nullptr, lay.frame_bytes, 0}, st);
     pl_adler32_launch(inflated, (int64_t)1 << 50, out_off, out_len, n, lay.frame_bytes, judge, trailer, 32, nullptr, d_status,
                       d_work + v->adler_slots, st);
   }
@@ -936,6 +928,18 @@ __host__ int pn_run(const char* who, const unsigned char* d_bytes, int64_t nbyte
 
 }  // namespace
 
+// the one place inflate_kernel is launched from outside zip_kernels.h (pl_common.h: tiff.hip's Deflate strips come through here)
+void pl_inflate_launch(bool checked, const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_in_off, const int64_t* d_in_len,
+                       int64_t n_streams, int wrapper, unsigned char* d_out, const int64_t* d_out_off, const int64_t* d_out_cap,
+                       int64_t* d_out_len, int32_t* d_status, PnChecked chk, hipStream_t st) {
+  if (checked)
+    hipLaunchKernelGGL(inflate_kernel<true>, dim3((unsigned)n_streams), dim3(PL_WAVE), 0, st, d_bytes, nbytes, d_in_off, d_in_len,
+                       wrapper, d_out, d_out_off, d_out_cap, d_out_len, d_status, chk);
+  else
+    hipLaunchKernelGGL(inflate_kernel<false>, dim3((unsigned)n_streams), dim3(PL_WAVE), 0, st, d_bytes, nbytes, d_in_off, d_in_len,
+                       wrapper, d_out, d_out_off, d_out_cap, d_out_len, d_status, chk);
+}
+
 extern "C" int pl_inflate(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_in_off, const int64_t* d_in_len,
                           int64_t n_streams, int wrapper, unsigned char* d_out, const int64_t* d_out_off, const int64_t* d_out_cap,
                           int64_t* d_out_len, int32_t* d_status, void* stream) {
@@ -949,8 +953,8 @@ extern "C" int pl_inflate(const unsigned char* d_bytes, int64_t nbytes, const in
     pl_set_error("pl_inflate: memset failed");
     return PL_ERR_HIP;
   }
-  hipLaunchKernelGGL(inflate_kernel<false>, dim3((unsigned)n_streams), dim3(PL_WAVE), 0, st, d_bytes, nbytes, d_in_off, d_in_len,
-                     wrapper, d_out, d_out_off, d_out_cap, d_out_len, d_status, PnChecked{});
+  pl_inflate_launch(false, d_bytes, nbytes, d_in_off, d_in_len, n_streams, wrapper, d_out, d_out_off, d_out_cap, d_out_len, d_status,
+                    PnChecked{}, st);
   return pl_check_launch("pl_inflate");
 }
 
@@ -1027,8 +1031,8 @@ extern "C" int pl_inflate_checked(const unsigned char* d_bytes, int64_t nbytes, 
   }
   uint32_t* trailer = reinterpret_cast<uint32_t*>(d_work + lay.trailer);
   int32_t* judge = reinterpret_cast<int32_t*>(d_work + lay.judge);
-  hipLaunchKernelGGL(inflate_kernel<true>, dim3((unsigned)n_streams), dim3(PL_WAVE), 0, st, d_bytes, nbytes, d_in_off, d_in_len, 1,
-                     d_out, d_out_off, d_out_cap, d_out_len, d_status, PnChecked{trailer, judge, d_in_used, max_out, 16});
+  pl_inflate_launch(true, d_bytes, nbytes, d_in_off, d_in_len, n_streams, 1, d_out, d_out_off, d_out_cap, d_out_len, d_status,
+                    PnChecked{trailer, judge, d_in_used, max_out, 16}, st);
   // the checksum of what was STORED, for the streams that ended where they should (the caller owns d_out: its size is unknown
   // here, and the Adler kernels read no dword outside a range)
   pl_adler32_launch(d_out, (int64_t)1 << 50, d_out_off, d_out_len, n_streams, max_out, judge, trailer, 8, nullptr, d_status,

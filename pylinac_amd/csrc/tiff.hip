@@ -1,4 +1,4 @@
-// Strip TIFFs (TIFF 6.0: uncompressed, PackBits 32773, LZW 5 with the horizontal predictor) -> typed frames on the device:
+// Strip TIFFs (TIFF 6.0: uncompressed, PackBits 32773, LZW 5 and Deflate 8 / 32946 with the horizontal predictor) -> typed frames on the device:
 // the step BEFORE the hot path for scanned film, next to dicom.hip and xim.hip.  The reference hands its analyzers
 // `np.asarray(PIL.Image.open(f))` (libtiff); the arithmetic here is libtiff's:
 //   * a strip holds rows_in_strip x row_bytes bytes (row_bytes = width x samples x bits / 8), rows one after the other;
@@ -17,6 +17,13 @@
 //   6 tiff_lzw_kernel     LZW strips, one wave per strip (below)
 //   7 tiff_finish_kernel  a wave per row of the staged bytes: byte swap, predictor scan, RGB collapse, store as out_kind
 // Launches 2, 3-5 and 6 are left out when the caller's `compressions` mask says no strip needs them.
+//
+// Deflate strips (Compression 8 and 32946, mask bit 8: pl_tiff_decode_ex only) add five launches between 6 and 7, left out
+// like the others: tiff_deflate_table_kernel (where every strip's bytes go, and which strips are not the inflate's),
+// png.hip's inflate_kernel<true> with the zlib wrapper (pl_inflate_launch: one wave per strip, straight into the staged area --
+// a strip is one contiguous zlib stream, nothing is gathered), adler32.hip's pair over what was stored (pl_adler32_launch, for
+// the strips whose stream ended where it should with its field present) and tiff_deflate_verdict_kernel (per strip -> bits 1,
+// 3 and 4 of its frame's status).  Always checked: libtiff hands zlib the whole strip, and a wrong Adler-32 is an error there.
 //
 // LZW without a string table.  Let q be the position (in code order) of the last Clear before code position p.  Entry
 // 258 + j is made when the (j + 2)-th code after the Clear is read, and is the string of the (j + 1)-th code followed by the
@@ -39,6 +46,7 @@ namespace {
 
 constexpr int kTfThreads = 256;
 constexpr int kTfNone = 1, kTfLzw = 5, kTfPackbits = 32773;
+constexpr int kTfDeflate = 8, kTfDeflateOld = 32946;        // Adobe Deflate and the older code: one codec in libtiff
 constexpr int kTfRing = 4096;                               // table positions since a Clear that a code can name: 1 .. 3838
 constexpr int kTfWindow = 1024;                             // input bytes staged in LDS at a time
 constexpr int kTfLong = 8;                                  // strings longer than this are copied by the whole wave
@@ -49,13 +57,15 @@ struct TfStrip {
   int64_t off, len;
 };
 
+__device__ __forceinline__ bool tf_is_deflate(int comp) { return comp == kTfDeflate || comp == kTfDeflateOld; }
+
 __device__ __forceinline__ TfStrip tf_strip(const int64_t* __restrict__ strip_off, const int64_t* __restrict__ strip_len,
                                             const int32_t* __restrict__ desc, int64_t s, int64_t nbytes, int64_t max_strip_bytes,
                                             int64_t n_frames, int height, int compressions) {
   TfStrip t;
   t.frame = desc[4 * s], t.row0 = desc[4 * s + 1], t.rows = desc[4 * s + 2], t.comp = desc[4 * s + 3];
   t.off = strip_off[s], t.len = strip_len[s];
-  const int bit = t.comp == kTfNone ? 1 : (t.comp == kTfPackbits ? 2 : (t.comp == kTfLzw ? 4 : 0));
+  const int bit = t.comp == kTfNone ? 1 : (t.comp == kTfPackbits ? 2 : (t.comp == kTfLzw ? 4 : (tf_is_deflate(t.comp) ? 8 : 0)));
   // (differences of lengths, never sums of an offset and a length: nothing here can overflow)
   t.ok = t.frame >= 0 && t.frame < n_frames && t.row0 >= 0 && t.rows >= 1 && t.row0 < height && t.rows <= height - t.row0 &&
          t.off >= 0 && t.len >= 0 && t.off <= nbytes && t.len <= nbytes - t.off && t.len <= max_strip_bytes &&
@@ -273,7 +283,46 @@ tiff_lzw_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const i
   }
 }
 
-// ---- launch 7: byte order, predictor, RGB collapse, store -----------------------------------------------------------------
+// ---- the Deflate launches (mask bit 8; pl_tiff_decode_ex) --------------------------------------------------------------------
+// A strip of Compression 8 / 32946 is ONE zlib stream, contiguous in the file: png.hip's inflate_kernel<true> reads it where it
+// lies (the caller's strip_off / strip_len ARE its stream table) and stores straight into the staged area.  This kernel fills
+// the rest of what it reads: where a strip's bytes go, how many they are, and a per-STRIP status word whose bit 0 tells the
+// inflate to leave the strip alone (another compression, an unsound descriptor, a window outside the buffer).
+__global__ void __launch_bounds__(kTfThreads)
+tiff_deflate_table_kernel(const int64_t* __restrict__ strip_off, const int64_t* __restrict__ strip_len,
+                          const int32_t* __restrict__ desc, int64_t n_strips, int64_t nbytes, int64_t max_strip_bytes,
+                          int64_t n_frames, int height, int64_t row_bytes, int compressions, int64_t* __restrict__ out_off,
+                          int64_t* __restrict__ out_cap, int32_t* __restrict__ strip_status) {
+  const int64_t s = (int64_t)blockIdx.x * kTfThreads + threadIdx.x;
+  if (s >= n_strips) return;
+  const TfStrip t = tf_strip(strip_off, strip_len, desc, s, nbytes, max_strip_bytes, n_frames, height, compressions);
+  const bool mine = t.ok && tf_is_deflate(t.comp);
+  out_off[s] = mine ? ((int64_t)t.frame * height + t.row0) * row_bytes : 0;
+  out_cap[s] = mine ? t.rows * row_bytes : 0;
+  strip_status[s] = mine ? 0 : 1;
+}
+
+// What libtiff's ZIPDecode makes of a strip, as bits of its FRAME's status.  libtiff hands zlib the whole strip and room for
+// rows x row_bytes bytes, and is content once they are filled: the input may end anywhere after that (a cut Adler-32 field), the
+// stream may go on.  A field that is there and differs is zlib's "incorrect data check".  Strips the inflate skipped (bit 0 of
+// the strip's word) left out_len and the flags unwritten: nothing of them is read.
+__global__ void __launch_bounds__(kTfThreads)
+tiff_deflate_verdict_kernel(const int32_t* __restrict__ desc, int64_t n_strips, int64_t n_frames,
+                            const int32_t* __restrict__ strip_status, const int64_t* __restrict__ out_cap,
+                            const int64_t* __restrict__ out_len, int32_t* __restrict__ status) {
+  const int64_t s = (int64_t)blockIdx.x * kTfThreads + threadIdx.x;
+  if (s >= n_strips) return;
+  const int st = strip_status[s];
+  if (st & 1) return;
+  int bits = 0;
+  if ((st & 2) && out_len[s] < out_cap[s]) bits |= 2;       // the input ended first, or the stream ended below the strip's size
+  if (st & 4) bits |= 8;                                    // corrupt Deflate, a bad zlib header and FDICT included
+  if (st & 16) bits |= 16;                                  // the Adler-32 of what was stored differs from the stream's field
+  const int f = desc[4 * s];
+  if (bits && f >= 0 && f < n_frames) atomicOr(status + f, bits);
+}
+
+// ---- the last launch: byte order, predictor, RGB collapse, store -----------------------------------------------------------
 // OUT: 0 the container dtype (uint8 / uint16; int32 for RGB), 1 uint16, 2 float64 -- `array.astype(dtype)` of the container
 template <int OUT>
 __device__ __forceinline__ void tf_store(void* __restrict__ out, int64_t i, unsigned v, int container_bytes) {
@@ -340,20 +389,23 @@ tiff_finish_kernel(const unsigned char* __restrict__ staged, const int32_t* __re
 }
 
 struct TfLayout {
-  int64_t staged, pb_off, pb_len, pb_expect, pb_dst, pb_frame, pb_work, total;
+  int64_t staged, pb_off, pb_len, pb_expect, pb_dst, pb_frame, pb_work;
+  int64_t df_out_off, df_out_cap, df_out_len, df_status, df_trailer, df_judge, df_slots, frame_bytes, total;
 };
 
+// max_mask: 7 for pl_tiff_decode (as ever), 15 for pl_tiff_decode_ex
 __host__ bool tf_layout(int64_t n_frames, int64_t n_strips, int64_t max_strip_bytes, int width, int height, int bits,
-                        int samples_per_pixel, int compressions, TfLayout* lay) {
+                        int samples_per_pixel, int compressions, int max_mask, TfLayout* lay) {
   if (n_frames < 1 || n_frames > 65535 || n_strips < 1 || n_strips > ((int64_t)1 << 31) - 1) return false;
   if (width < 1 || height < 1 || max_strip_bytes < 0 || max_strip_bytes > ((int64_t)1 << 36)) return false;
   if (!((samples_per_pixel == 1 && (bits == 8 || bits == 16)) || (samples_per_pixel == 3 && bits == 8))) return false;
-  if (compressions < 1 || compressions > 7) return false;
+  if (compressions < 1 || compressions > max_mask) return false;
   const int64_t frame_bytes = (int64_t)width * height * samples_per_pixel * (bits / 8);
   if (frame_bytes > ((int64_t)1 << 31) - 1) return false;
   if ((compressions & 2) && n_strips > 65535) return false; // the PackBits passes put the stream on a grid axis
   auto up = [](int64_t v) { return (v + 15) & ~(int64_t)15; };
   int64_t at = 0;
+  lay->frame_bytes = frame_bytes;
   lay->staged = at, at += up(n_frames * frame_bytes);
   lay->pb_off = lay->pb_len = lay->pb_expect = lay->pb_dst = lay->pb_frame = lay->pb_work = -1;
   if (compressions & 2) {
@@ -364,39 +416,57 @@ __host__ bool tf_layout(int64_t n_frames, int64_t n_strips, int64_t max_strip_by
     lay->pb_frame = at, at += up(n_strips * 4);
     lay->pb_work = at, at += up(pl_packbits_work_bytes(n_strips, max_strip_bytes));
   }
+  lay->df_out_off = lay->df_out_cap = lay->df_out_len = lay->df_status = lay->df_trailer = lay->df_judge = lay->df_slots = -1;
+  if (compressions & 8) {
+    // a strip holds at most the frame: the bound of the Adler tiles (the host is not told the strips' rows)
+    const int64_t slots = pl_adler32_slots_bytes(n_strips, frame_bytes);
+    if (slots < 0) return false;
+    lay->df_out_off = at, at += up(n_strips * 8);
+    lay->df_out_cap = at, at += up(n_strips * 8);
+    lay->df_out_len = at, at += up(n_strips * 8);
+    lay->df_status = at, at += up(n_strips * 4);
+    lay->df_trailer = at, at += up(n_strips * 4);
+    lay->df_judge = at, at += up(n_strips * 4);             // (zeroed together with the trailers)
+    lay->df_slots = at, at += slots;
+  }
   lay->total = at;
   return true;
 }
 
-}  // namespace
+#define TF_REQUIRE(cond, msg)              \
+  do {                                     \
+    if (!(cond)) {                         \
+      pl_set_error("%s: %s", who, msg);    \
+      return PL_ERR_INVALID_ARG;           \
+    }                                      \
+  } while (0)
 
-extern "C" int64_t pl_tiff_work_bytes(int64_t n_frames, int64_t n_strips, int64_t max_strip_bytes, int width, int height,
-                                      int bits, int samples_per_pixel, int compressions) {
-  TfLayout lay;
-  return tf_layout(n_frames, n_strips, max_strip_bytes, width, height, bits, samples_per_pixel, compressions, &lay) ? lay.total : -1;
-}
-
-extern "C" int pl_tiff_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_strip_off,
-                              const int64_t* d_strip_len, const int32_t* d_strip_desc, int64_t n_strips,
-                              int64_t max_strip_bytes, const int32_t* d_frame_flags, int64_t n_frames, int width, int height,
-                              int bits, int samples_per_pixel, int compressions, void* d_out, int out_kind, int32_t* d_status,
-                              unsigned char* d_work, void* stream) {
+// pl_tiff_decode (max_mask 7) and pl_tiff_decode_ex (max_mask 15): one body, the Deflate launches only under mask bit 8
+__host__ int tf_decode(const char* who, int max_mask, const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_strip_off,
+                       const int64_t* d_strip_len, const int32_t* d_strip_desc, int64_t n_strips, int64_t max_strip_bytes,
+                       const int32_t* d_frame_flags, int64_t n_frames, int width, int height, int bits, int samples_per_pixel,
+                       int compressions, void* d_out, int out_kind, int32_t* d_status, unsigned char* d_work, void* stream) {
   if (!((samples_per_pixel == 1 && (bits == 8 || bits == 16)) || (samples_per_pixel == 3 && bits == 8))) {
-    pl_set_error("pl_tiff_decode: unsupported samples (%d x %d bits): grey of 8 or 16 bits, RGB of 8", samples_per_pixel, bits);
+    pl_set_error("%s: unsupported samples (%d x %d bits): grey of 8 or 16 bits, RGB of 8", who, samples_per_pixel, bits);
     return PL_ERR_UNSUPPORTED;
   }
-  PL_REQUIRE(d_bytes && d_strip_off && d_strip_len && d_strip_desc && d_frame_flags && d_out && d_status && d_work, "null pointer");
-  PL_REQUIRE(((uintptr_t)d_bytes & 3) == 0, "the byte buffer must start on a 4-byte boundary (strips inside it may start anywhere)");
-  PL_REQUIRE(((uintptr_t)d_work & 15) == 0, "d_work must start on a 16-byte boundary");
-  PL_REQUIRE(out_kind >= 0 && out_kind <= 2, "out_kind 0 (container dtype), 1 (uint16) or 2 (float64)");
-  PL_REQUIRE(nbytes >= 0, "bad buffer size");
+  TF_REQUIRE(d_bytes && d_strip_off && d_strip_len && d_strip_desc && d_frame_flags && d_out && d_status && d_work, "null pointer");
+  TF_REQUIRE(((uintptr_t)d_bytes & 3) == 0, "the byte buffer must start on a 4-byte boundary (strips inside it may start anywhere)");
+  TF_REQUIRE(((uintptr_t)d_work & 15) == 0, "d_work must start on a 16-byte boundary");
+  TF_REQUIRE(out_kind >= 0 && out_kind <= 2, "out_kind 0 (container dtype), 1 (uint16) or 2 (float64)");
+  TF_REQUIRE(nbytes >= 0, "bad buffer size");
   TfLayout lay;
-  PL_REQUIRE(tf_layout(n_frames, n_strips, max_strip_bytes, width, height, bits, samples_per_pixel, compressions, &lay),
-             "1 <= n_frames <= 65535, n_strips >= 1 (<= 65535 with PackBits), width, height >= 1, a frame below 2 GiB, "
-             "compressions a mask of 1 (none) | 2 (PackBits) | 4 (LZW)");
+  TF_REQUIRE(tf_layout(n_frames, n_strips, max_strip_bytes, width, height, bits, samples_per_pixel, compressions, max_mask, &lay),
+             max_mask == 7 ? "1 <= n_frames <= 65535, n_strips >= 1 (<= 65535 with PackBits), width, height >= 1, a frame below 2 GiB, "
+                             "compressions a mask of 1 (none) | 2 (PackBits) | 4 (LZW)"
+                           : "1 <= n_frames <= 65535, n_strips >= 1 (<= 65535 with PackBits), width, height >= 1, a frame below 2 GiB "
+                             "(at most 65535 x 16 KiB with Deflate), compressions a mask of 1 (none) | 2 (PackBits) | 4 (LZW) | 8 (Deflate)");
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(d_status, 0, (size_t)n_frames * 4, st) != hipSuccess) {
-    pl_set_error("pl_tiff_decode: memset failed");
+  bool zeroed = hipMemsetAsync(d_status, 0, (size_t)n_frames * 4, st) == hipSuccess;
+  if (compressions & 8)
+    zeroed = zeroed && hipMemsetAsync(d_work + lay.df_trailer, 0, (size_t)(lay.df_slots - lay.df_trailer), st) == hipSuccess;
+  if (!zeroed) {
+    pl_set_error("%s: memset failed", who);
     return PL_ERR_HIP;
   }
   const int ib = bits / 8;
@@ -425,6 +495,24 @@ extern "C" int pl_tiff_decode(const unsigned char* d_bytes, int64_t nbytes, cons
   if (compressions & 4)
     hipLaunchKernelGGL(tiff_lzw_kernel, dim3((unsigned)n_strips), dim3(PL_WAVE), 0, st, d_bytes, nbytes, d_strip_off, d_strip_len,
                        d_strip_desc, max_strip_bytes, n_frames, height, row_bytes, compressions, staged, d_status);
+  if (compressions & 8) {
+    int64_t* out_off = reinterpret_cast<int64_t*>(d_work + lay.df_out_off);
+    int64_t* out_cap = reinterpret_cast<int64_t*>(d_work + lay.df_out_cap);
+    int64_t* out_len = reinterpret_cast<int64_t*>(d_work + lay.df_out_len);
+    int32_t* strip_status = reinterpret_cast<int32_t*>(d_work + lay.df_status);
+    uint32_t* trailer = reinterpret_cast<uint32_t*>(d_work + lay.df_trailer);
+    int32_t* judge = reinterpret_cast<int32_t*>(d_work + lay.df_judge);
+    const dim3 per_strip((unsigned)pl_cdiv(n_strips, kTfThreads));
+    hipLaunchKernelGGL(tiff_deflate_table_kernel, per_strip, dim3(kTfThreads), 0, st, d_strip_off, d_strip_len, d_strip_desc, n_strips,
+                       nbytes, max_strip_bytes, n_frames, height, row_bytes, compressions, out_off, out_cap, strip_status);
+    // a stream that goes on beyond the strip's rows is no error (libtiff stops reading there): overflow 0, not judged
+    pl_inflate_launch(true, d_bytes, nbytes, d_strip_off, d_strip_len, n_strips, 1, staged, out_off, out_cap, out_len, strip_status,
+                      PnChecked{trailer, judge, nullptr, lay.frame_bytes, 0}, st);
+    pl_adler32_launch(staged, n_frames * lay.frame_bytes, out_off, out_len, n_strips, lay.frame_bytes, judge, trailer, 16, nullptr,
+                      strip_status, d_work + lay.df_slots, st);
+    hipLaunchKernelGGL(tiff_deflate_verdict_kernel, per_strip, dim3(kTfThreads), 0, st, d_strip_desc, n_strips, n_frames,
+                       strip_status, out_cap, out_len, d_status);
+  }
   const dim3 grid((unsigned)pl_cdiv(height, kTfThreads / PL_WAVE), (unsigned)n_frames);
 #define TF_FINISH(BYTES, SPP, OUT)                                                                                            \
   hipLaunchKernelGGL((tiff_finish_kernel<BYTES, SPP, OUT>), grid, dim3(kTfThreads), 0, st, staged, d_frame_flags, width, height, \
@@ -438,5 +526,40 @@ extern "C" int pl_tiff_decode(const unsigned char* d_bytes, int64_t nbytes, cons
   else { TF_OUT(2, 1); }
 #undef TF_OUT
 #undef TF_FINISH
-  return pl_check_launch("pl_tiff_decode");
+  return pl_check_launch(who);
+}
+#undef TF_REQUIRE
+
+}  // namespace
+
+extern "C" int64_t pl_tiff_work_bytes(int64_t n_frames, int64_t n_strips, int64_t max_strip_bytes, int width, int height,
+                                      int bits, int samples_per_pixel, int compressions) {
+  TfLayout lay;
+  return tf_layout(n_frames, n_strips, max_strip_bytes, width, height, bits, samples_per_pixel, compressions, 7, &lay) ? lay.total : -1;
+}
+
+extern "C" int64_t pl_tiff_work_bytes_ex(int64_t n_frames, int64_t n_strips, int64_t max_strip_bytes, int width, int height,
+                                         int bits, int samples_per_pixel, int compressions) {
+  TfLayout lay;
+  return tf_layout(n_frames, n_strips, max_strip_bytes, width, height, bits, samples_per_pixel, compressions, 15, &lay) ? lay.total : -1;
+}
+
+extern "C" int pl_tiff_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_strip_off,
+                              const int64_t* d_strip_len, const int32_t* d_strip_desc, int64_t n_strips,
+                              int64_t max_strip_bytes, const int32_t* d_frame_flags, int64_t n_frames, int width, int height,
+                              int bits, int samples_per_pixel, int compressions, void* d_out, int out_kind, int32_t* d_status,
+                              unsigned char* d_work, void* stream) {
+  return tf_decode("pl_tiff_decode", 7, d_bytes, nbytes, d_strip_off, d_strip_len, d_strip_desc, n_strips, max_strip_bytes,
+                   d_frame_flags, n_frames, width, height, bits, samples_per_pixel, compressions, d_out, out_kind, d_status, d_work,
+                   stream);
+}
+
+extern "C" int pl_tiff_decode_ex(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_strip_off,
+                                 const int64_t* d_strip_len, const int32_t* d_strip_desc, int64_t n_strips,
+                                 int64_t max_strip_bytes, const int32_t* d_frame_flags, int64_t n_frames, int width, int height,
+                                 int bits, int samples_per_pixel, int compressions, void* d_out, int out_kind, int32_t* d_status,
+                                 unsigned char* d_work, void* stream) {
+  return tf_decode("pl_tiff_decode_ex", 15, d_bytes, nbytes, d_strip_off, d_strip_len, d_strip_desc, n_strips, max_strip_bytes,
+                   d_frame_flags, n_frames, width, height, bits, samples_per_pixel, compressions, d_out, out_kind, d_status, d_work,
+                   stream);
 }

@@ -7,6 +7,11 @@ files, still compressed, laid at 4-byte boundaries of one pinned buffer -> one c
 per-strip descriptor table -> ``TiffStack`` with ``[N, H, W]`` frames and a per-file status, nothing read back unless
 ``check``.  The values are ``np.asarray(PIL.Image.open(f))`` -- what the reference's ``FileImage`` hands its analyzers --
 for grey files, and PIL's ``convert("I")`` of an RGB file.
+
+Deflate strips (Compression 8, "Adobe Deflate", and 32946: what GIMP, Python writers and scanners' "compressed TIFF" make)
+are opt-in: ``load_frames(..., deflate=True)`` and a ``compressions`` mask with bit 8 go through ``pl_tiff_decode_ex``, where
+every strip -- one zlib stream -- is inflated by one wave of the device and its Adler-32 is checked, as libtiff does (status
+bits ``STATUS_CORRUPT_DEFLATE`` and ``STATUS_ADLER``).  Without the keyword such files are refused as before.
 """
 from __future__ import annotations
 
@@ -23,8 +28,11 @@ from ._stack_io import (FileStack, bytes_tensor, file_name, frames_out, index_te
                         source_bytes, trim_frames)
 
 COMPRESSION_NONE, COMPRESSION_LZW, COMPRESSION_PACKBITS = 1, 5, 32773
+COMPRESSION_DEFLATE, COMPRESSION_DEFLATE_OLD = 8, 32946
 _COMPRESSION_BIT = {COMPRESSION_NONE: 1, COMPRESSION_PACKBITS: 2, COMPRESSION_LZW: 4}
+_DEFLATE_BIT = {COMPRESSION_DEFLATE: 8, COMPRESSION_DEFLATE_OLD: 8}      # (pl_tiff_decode_ex only)
 STATUS_WINDOW, STATUS_SHORT, STATUS_CORRUPT_LZW = 1, 2, 4
+STATUS_CORRUPT_DEFLATE, STATUS_ADLER = 8, 16
 # TIFF 6.0 field types -> (struct code, bytes); SHORT, LONG and RATIONAL are what the tags read here may have
 _TYPES = {1: ("B", 1), 3: ("H", 2), 4: ("I", 4), 5: ("II", 8)}
 _TAGS = (256, 257, 258, 259, 262, 273, 277, 278, 279, 282, 283, 284, 296, 317, 338, 339, 322)
@@ -155,19 +163,24 @@ def read_tiff(source, _what: str | None = None) -> TiffInfo:
                     bits_per_sample=bps, path=source if isinstance(source, (str, Path)) else None, tags=tags)
 
 
-def _refuse(info: TiffInfo, data, what: str):
-    """ValueError for what the kernels do not decode, naming the file (before anything is copied)"""
+def _refuse(info: TiffInfo, data, what: str, deflate: bool = False):
+    """ValueError for what the kernels do not decode, naming the file (before anything is copied).  ``deflate``: Compression
+    8 / 32946 passes, with Predictor 1 or 2; every other message is what it is without it."""
     def no(text):
         raise ValueError(f"load_frames: {what}: {text}")
 
+    deflated = deflate and info.compression in _DEFLATE_BIT
     if info.tiled:
         no("tiled TIFFs (tag 322 TileWidth) are not supported, strips only")
-    if info.compression not in _COMPRESSION_BIT:
-        no(f"Compression {info.compression} is not supported: 1 (none), 32773 (PackBits) or 5 (LZW)")
+    if info.compression not in _COMPRESSION_BIT and not deflated:
+        no(f"Compression {info.compression} is not supported: 1 (none), 32773 (PackBits) or 5 (LZW)"
+           + ("; 8 or 32946 (Deflate)" if deflate else ""))
     if info.predictor not in (1, 2):
-        no(f"Predictor {info.predictor} is not supported: 1, or 2 (horizontal differencing) with LZW")
-    if info.predictor == 2 and info.compression != COMPRESSION_LZW:
-        no(f"Predictor 2 with Compression {info.compression} is not supported (LZW only)")
+        no(f"Predictor {info.predictor} is not supported: 1, or 2 (horizontal differencing) with LZW"
+           + (" or Deflate" if deflate else ""))
+    if info.predictor == 2 and info.compression != COMPRESSION_LZW and not deflated:
+        no(f"Predictor 2 with Compression {info.compression} is not supported (LZW only"
+           + (", or Deflate)" if deflate else ")"))
     if info.planar != 1:
         no(f"PlanarConfiguration {info.planar} is not supported (1, chunky)")
     if info.sample_format != 1:
@@ -199,15 +212,16 @@ def decode_tiff_strips(buffer, strip_off, strip_len, strip_desc, frame_flags, wi
     """``pl_tiff_decode``: strips anywhere inside ``buffer`` (uint8 array / tensor; a device tensor is used in place) ->
     (frames [N, height, width], status int32 [N]), both on the device, nothing read back.  ``strip_off`` / ``strip_len``
     int64 [S]; ``strip_desc`` int32 [S, 4] = frame, first row, rows, Compression; ``frame_flags`` int32 [N]: bit 0 Predictor
-    2, bit 1 big-endian samples.  ``compressions`` (mask 1 none | 2 PackBits | 4 LZW) and ``max_strip_bytes`` are derived from
-    host arrays when not given.  ``out``: a device tensor to decode into.  status bits: 1 a strip outside the buffer or an
-    unsound descriptor (nothing of the frame is stored), 2 a short strip, 4 corrupt LZW."""
+    2, bit 1 big-endian samples.  ``compressions`` (mask 1 none | 2 PackBits | 4 LZW | 8 Deflate: descriptors 8 and 32946) and
+    ``max_strip_bytes`` are derived from host arrays when not given; a mask with bit 8 goes through ``pl_tiff_decode_ex``.
+    ``out``: a device tensor to decode into.  status bits: 1 a strip outside the buffer or an unsound descriptor (nothing of
+    the frame is stored), 2 a short strip, 4 corrupt LZW, 8 corrupt Deflate, 16 a Deflate strip's Adler-32 differs."""
     kind = out_kind(dtype)
     dev = on_device(device)
     if compressions is None:
         compressions = 0
         for c in np.unique(np.asarray(strip_desc.cpu() if isinstance(strip_desc, torch.Tensor) else strip_desc)[:, 3]):
-            compressions |= _COMPRESSION_BIT.get(int(c), 0)
+            compressions |= _COMPRESSION_BIT.get(int(c), 0) | _DEFLATE_BIT.get(int(c), 0)
         compressions = compressions or 1
     if max_strip_bytes is None:
         max_strip_bytes = int(np.asarray(strip_len.cpu() if isinstance(strip_len, torch.Tensor) else strip_len).max(initial=0))
@@ -219,14 +233,16 @@ def decode_tiff_strips(buffer, strip_off, strip_len, strip_desc, frame_flags, wi
     if off.dim() != 1 or int(ln.numel()) != n_strips or tuple(desc.shape) != (n_strips, 4) or flags.dim() != 1:
         raise ValueError("decode_tiff_strips: strip_off / strip_len [S], strip_desc [S, 4], frame_flags [N]")
     lib = _lib.load()
-    nwork = int(lib.pl_tiff_work_bytes(n, n_strips, max_strip_bytes, width, height, bits, samples, compressions))
+    ex = bool(compressions & 8)                           # (the older entries go on refusing masks above 7)
+    work_bytes, decode, who = ((lib.pl_tiff_work_bytes_ex, lib.pl_tiff_decode_ex, "pl_tiff_decode_ex") if ex else
+                               (lib.pl_tiff_work_bytes, lib.pl_tiff_decode, "pl_tiff_decode"))
+    nwork = int(work_bytes(n, n_strips, max_strip_bytes, width, height, bits, samples, compressions))
     work = torch.empty(max(nwork, 16), dtype=torch.uint8, device=dev)
     out = frames_out(out, "decode_tiff_strips", n, height, width, bits, samples, kind, dev)
     status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    _check(lib.pl_tiff_decode(buf.data_ptr(), buf.numel(), off.data_ptr(), ln.data_ptr(), desc.data_ptr(), n_strips,
-                              max_strip_bytes, flags.data_ptr(), n, width, height, bits, samples, compressions, out.data_ptr(),
-                              kind, status.data_ptr(), work.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-           "pl_tiff_decode")
+    _check(decode(buf.data_ptr(), buf.numel(), off.data_ptr(), ln.data_ptr(), desc.data_ptr(), n_strips, max_strip_bytes,
+                  flags.data_ptr(), n, width, height, bits, samples, compressions, out.data_ptr(), kind, status.data_ptr(),
+                  work.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), who)
     return trim_frames(out, n, height, width), status[:n]
 
 
@@ -236,13 +252,13 @@ class TiffStack(FileStack):
     FORMAT = "TIFF"
 
 
-def _stage(sources, device=None):
+def _stage(sources, device=None, deflate: bool = False):
     """The host half of ``load_frames``: every file's IFD walked and judged, then the files laid at 4-byte boundaries of one
     pinned buffer and ONE copy of it queued -> (images, device buffer, strip offsets, lengths, descriptors, frame flags,
     compression mask, longest strip)."""
     def parse(data, k, what):
         info = read_tiff(data, _what=what)
-        _refuse(info, data, what)
+        _refuse(info, data, what, deflate)
         return info
 
     images, starts, host, dbuf = pack_files(sources, device, parse)
@@ -256,7 +272,7 @@ def _stage(sources, device=None):
     off, ln, desc, flags, mask = [], [], [], [], 0
     for k, (st, x) in enumerate(zip(starts, images)):
         flags.append((1 if x.predictor == 2 else 0) | (2 if x.byte_order == "MM" and x.bits == 16 else 0))
-        mask |= _COMPRESSION_BIT[x.compression]
+        mask |= _COMPRESSION_BIT.get(x.compression) or _DEFLATE_BIT[x.compression]
         for o, c, row0, rows in x.strips:
             off.append(st + o)
             ln.append(c)
@@ -272,7 +288,7 @@ def _stage(sources, device=None):
     return (images, dbuf, table[:s], table[s:], small[:4 * s].reshape(s, 4), small[4 * s:], mask, max(ln, default=0))
 
 
-def load_frames(sources, dtype=None, dpi=None, device=None, check: bool = True) -> TiffStack:
+def load_frames(sources, dtype=None, dpi=None, device=None, check: bool = True, deflate: bool = False) -> TiffStack:
     """The batched loader the reference does not have: strip TIFFs (paths, bytes or binary file objects) of ONE width,
     height, BitsPerSample and SamplesPerPixel -> ``TiffStack``.  Files may differ in compression (none, PackBits, LZW),
     predictor, byte order and strip layout.  Grey files of 8 or 16 bits give uint8 / uint16 frames (``dtype=np.uint16`` or
@@ -281,9 +297,14 @@ def load_frames(sources, dtype=None, dpi=None, device=None, check: bool = True) 
     palette images, 1-, 4- and 32-bit and float samples, 16-bit RGB, ExtraSamples, old-style LZW) raises ``ValueError`` naming
     the file before anything is copied.  ``dpi`` overrides the files' resolution tags, as ``FileImage(path, dpi=...)`` does.
     ``check=True`` reads the status once and raises ``OSError`` naming the first flagged file (PIL raises ``OSError`` for a
-    truncated or corrupt strip); ``check=False`` transfers nothing back."""
+    truncated or corrupt strip); ``check=False`` transfers nothing back.
+
+    ``deflate=True`` also accepts Compression 8 and 32946 (Deflate), with Predictor 1 or 2, in the same sample formats and
+    mixed with the others in one stack.  Every strip is inflated on the device and checked as libtiff checks it: corrupt
+    Deflate data (a bad zlib header included) and an Adler-32 that differs from the stream's field flag the file; bytes
+    behind the stream, a field that is cut off and a stream longer than the strip's rows do not."""
     out_kind(dtype)                        # TypeError before any file is read
-    images, dbuf, off, ln, desc, flags, mask, longest = _stage(sources, device)
+    images, dbuf, off, ln, desc, flags, mask, longest = _stage(sources, device, deflate)
     first = images[0]
     frames, status = decode_tiff_strips(dbuf, off, ln, desc, flags, first.width, first.height, first.bits, first.samples,
                                         dtype=dtype, device=dbuf.device, compressions=mask, max_strip_bytes=longest)
@@ -293,6 +314,8 @@ def load_frames(sources, dtype=None, dpi=None, device=None, check: bool = True) 
         for k in np.flatnonzero(got):
             what = ("a strip lies outside the file" if got[k] & STATUS_WINDOW else
                     "corrupt LZW data (a code names a table entry that does not exist)" if got[k] & STATUS_CORRUPT_LZW else
+                    "corrupt Deflate data in a strip" if got[k] & STATUS_CORRUPT_DEFLATE else
+                    "the Adler-32 of a strip differs from the checksum its stream ends with" if got[k] & STATUS_ADLER else
                     "a strip decodes to fewer bytes than its rows hold")
             raise OSError(f"load_frames: {file_name(images, int(k))}: {what}")
     return stack
