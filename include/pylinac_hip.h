@@ -630,7 +630,8 @@ int pl_tiff_decode_ex(const unsigned char* d_bytes, int64_t nbytes, const int64_
  *   d_status int32 [n_streams] (zeroed here): bit 0 the stream's window does not lie inside [0, nbytes) or d_out_cap[i] is
  *   negative or above 2^31 - 1 (nothing stored), bit 1 the input ended first or the stream ended below d_out_cap[i] bytes,
  *   bit 2 corrupt Deflate: a bad zlib header, block type 3, LEN != ~NLEN, an over-subscribed code set, an incomplete one
- *   (other than no distance code at all or the single one-bit distance code RFC 1951 allows), no end-of-block code, HLIT
+ *   (other than no distance code at all, the single one-bit distance code RFC 1951 allows, or a literal/length set that is
+ *   the single one-bit end-of-block code, which zlib accepts: a block without output), no end-of-block code, HLIT
  *   above 286 or HDIST above 30, literal/length symbol 286 / 287, distance symbol 30 / 31, a repeat code 16 with nothing to
  *   repeat, a code-length run past HLIT + HDIST, a distance that reaches before the start of the output.
  * pl_png_decode replaces `np.asarray(PIL.Image.open(f))` for a STACK of PNG files of one width, height, bit depth and colour

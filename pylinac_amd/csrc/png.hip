@@ -272,6 +272,22 @@ struct PnIn {                                               // the bit reader: a
   int64_t pos, win0;                                        // the next input byte to enter `buf`; the window's first byte
 };
 
+// A match with dist + n > kPnRing (every lane calls this; zlib's encoder never writes one: it stops at distance 32 506).  The
+// ring holds kPnRing bytes of output, so the slot byte k of the match is read from is the slot byte k + (kPnRing - dist) of the
+// SAME match is stored to (dist = 32768: the lane's own slot).  64 bytes at a time: every lane loads its byte, the wave meets,
+// then the lanes store -- a later byte's store never precedes an earlier byte's load, within a step by the barrier and across
+// steps by their order, without any reliance on the lanes running in lock-step.  Kept out of line, behind a branch marked
+// unlikely: inlined, or unmarked, it cost the whole of inflate_kernel 0.3 - 5 % through the register allocation around it; as it
+// stands the common path pays one scalar compare a match (profiles/deflate_conformance_time.md).
+__device__ __attribute__((noinline)) void pn_copy_alias(unsigned char* ring, unsigned op, unsigned dist, unsigned n, int lane) {
+  for (unsigned k0 = 0; k0 < n; k0 += PL_WAVE) {
+    const unsigned k = k0 + (unsigned)lane;
+    const unsigned char held = k < n ? ring[(op + k - dist) & (kPnRing - 1)] : (unsigned char)0;
+    pl_wave_sync();
+    if (k < n) ring[(op + k) & (kPnRing - 1)] = held;
+  }
+}
+
 // CHECKED (pl_inflate_checked, pl_png_decode_checked, tiff.hip's Deflate strips): what the wave reports besides, per stream
 // (PnChecked, pl_common.h).  In that mode it does not stop at out_cap bytes but decodes on to the end-of-block code of the
 // BFINAL block -- storing nothing beyond out_cap, and giving up at the first byte beyond it, which settles the verdict -- drops
@@ -482,7 +498,10 @@ inflate_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const in
       pl_wave_sync();
       if (lane < 32) s_lens[288 + lane] = lane < hdist ? keep : (unsigned char)0;
       pl_wave_sync();
-      if (pn_build(s_lens, hlit, s_lit, kPnLitBits, s_litsym, &s_lc, lane, &coded, &longest) != 0) {
+      const int lk = pn_build(s_lens, hlit, s_lit, kPnLitBits, s_litsym, &s_lc, lane, &coded, &longest);
+      // the one incomplete literal/length set zlib's inftrees.c allows: ONE code of one bit (the end-of-block code, by the
+      // check above: a block without output)
+      if (lk == 1 || (lk == 2 && !(coded == 1 && longest == 1))) {
         flag = 4;
         break;
       }
@@ -581,9 +600,12 @@ inflate_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const in
       }
       if (n > lim - op) n = lim - op;
       pl_wave_sync();
-      // byte k of the match = byte k mod dist of the `dist` bytes before it (they lie wholly before the match: every lane
-      // reads bytes that this token does not write; dist = 32768 and k names the slot the same lane is about to fill)
-      if (dist >= n) {
+      // byte k of the match = byte k mod dist of the `dist` bytes before it.  Those bytes lie wholly before the match in the
+      // OUTPUT; in the RING they do only while dist + n <= kPnRing: beyond that, source and target share slots and the copy
+      // is pn_copy_alias's.  In the three branches below every lane reads slots that this token does not write
+      if (__builtin_expect(dist + n > (unsigned)kPnRing, 0)) {
+        pn_copy_alias(ring, op, dist, n, lane);
+      } else if (dist >= n) {
         for (unsigned k = lane; k < n; k += PL_WAVE) ring[(op + k) & (kPnRing - 1)] = ring[(op + k - dist) & (kPnRing - 1)];
       } else if (dist == 1) {
         const unsigned char v = ring[(op - 1u) & (kPnRing - 1)];

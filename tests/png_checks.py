@@ -135,12 +135,20 @@ def inflate_trace(raw: bytes, limit: int | None = None):
     """a bit-serial inflate of a RAW stream -> (bytes, trace): block types seen, the largest distance, counts of distance-1,
     length-258 and overlapping (1 < distance < length) matches, of matches whose source lies before a 4 KiB flush boundary of
     their target and of those at distance 32768, the code-length symbols used, the bit span of every Huffman code and the
-    byte position of every stored block's LEN field.  Raises ValueError for corrupt or truncated data."""
+    byte position of every stored block's LEN field; besides, ``ring_alias`` counts the matches with distance + length > 32768
+    (the 32 KiB ring then holds source and target of the copy in the same slots) and ``alias`` lists (32768 - distance, length,
+    output position) of each, ``max_lit_code`` / ``max_dist_code`` are the longest literal/length and distance codes that
+    occur, ``len_syms`` / ``dist_syms`` the length and distance symbols used, ``stored_sizes`` the LEN of every stored block,
+    and per dynamic block ``dist_codes`` has the number of distance codes, ``headers`` (HLIT, HDIST) and ``cl_cross`` the
+    repeat symbols whose run begins in the literal/length lengths and ends in the distance lengths.  Incomplete sets pass as
+    in zlib's inftrees.c: only ONE code of one bit (or, for distances, no code at all).  Raises ValueError for corrupt or
+    truncated data."""
     pos = 0
     nbits = len(raw) * 8
     out = bytearray()
     tr = dict(types=set(), max_dist=0, dist1=0, len258=0, overlap=0, across_flush=0, dist32768=0, cl_syms=set(), codes=[],
-              len_fields=[])
+              len_fields=[], ring_alias=0, alias=[], max_lit_code=0, max_dist_code=0, len_syms=set(), dist_syms=set(),
+              stored_sizes=[], dist_codes=[], headers=[], cl_cross=set())
 
     def bits(n):
         nonlocal pos
@@ -171,12 +179,14 @@ def inflate_trace(raw: bytes, limit: int | None = None):
                 nxt[l] += 1
         return t, left
 
-    def symbol(t):
+    def symbol(t, longest=None):
         start, code = pos, 0
         for l in range(1, 16):
             code = (code << 1) | bits(1)
             if (l, code) in t:
                 tr["codes"].append((start, pos))
+                if longest:
+                    tr[longest] = max(tr[longest], l)
                 return t[(l, code)]
         raise ValueError("invalid code")
 
@@ -192,6 +202,7 @@ def inflate_trace(raw: bytes, limit: int | None = None):
                 raise ValueError("LEN != ~NLEN")
             if (pos >> 3) + n > len(raw):
                 raise ValueError("truncated")
+            tr["stored_sizes"].append(n)
             out += raw[pos >> 3:(pos >> 3) + n]
             pos += 8 * n
         elif typ == 3:
@@ -215,20 +226,27 @@ def inflate_trace(raw: bytes, limit: int | None = None):
                         lens.append(s)
                         continue
                     tr["cl_syms"].add(s)
+                    before = len(lens)
                     if s == 16:
                         if not lens:
                             raise ValueError("nothing to repeat")
                         lens += [lens[-1]] * (3 + bits(2))
                     else:
                         lens += [0] * ((3 + bits(3)) if s == 17 else (11 + bits(7)))
+                    if before < hlit < len(lens):
+                        tr["cl_cross"].add(s)
                 if len(lens) > hlit + hdist:
                     raise ValueError("run past HLIT + HDIST")
                 lit, left = table(lens[:hlit])
-                if left:
+                if left and max(lens[:hlit]) != 1:                                 # (inftrees.c: left > 0 && max != 1)
                     raise ValueError("incomplete literal/length set")
                 dist, left = table(lens[hlit:])
+                if left and max(lens[hlit:]) > 1:
+                    raise ValueError("incomplete distance set")
+                tr["dist_codes"].append(len(dist))
+                tr["headers"].append((hlit, hdist))
             while True:
-                s = symbol(lit)
+                s = symbol(lit, "max_lit_code")
                 if s < 256:
                     out.append(s)
                 elif s == 256:
@@ -237,9 +255,10 @@ def inflate_trace(raw: bytes, limit: int | None = None):
                     if s > 285:
                         raise ValueError("length symbol")
                     n = _LEN_BASE[s - 257] + bits(_LEN_EXTRA[s - 257])
-                    d = symbol(dist)
+                    d = symbol(dist, "max_dist_code")
                     if d > 29:
                         raise ValueError("distance symbol")
+                    tr["len_syms"].add(s), tr["dist_syms"].add(d)
                     d = _DIST_BASE[d] + bits(_DIST_EXTRA[d])
                     if d > len(out):
                         raise ValueError("distance before the start")
@@ -250,6 +269,9 @@ def inflate_trace(raw: bytes, limit: int | None = None):
                     tr["overlap"] += 1 < d < n
                     tr["across_flush"] += (at - d) // 4096 < at // 4096
                     tr["dist32768"] += d == 32768
+                    if d + n > 32768:
+                        tr["ring_alias"] += 1
+                        tr["alias"].append((32768 - d, n, at))
                     for k in range(n):
                         out.append(out[at - d + k])
                 if limit is not None and len(out) >= limit:
