@@ -571,6 +571,36 @@ int64_t pl_dicom_rle_work_bytes(int64_t n_frames, int segments, int64_t max_segm
 int pl_dicom_rle_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_seg_off, const int64_t* d_seg_len,
                         int64_t n_frames, int segments, int64_t max_segment_bytes, int rows, int cols,
                         unsigned char* d_native, int32_t* d_status, unsigned char* d_work, void* stream);
+/* JPEG Lossless Pixel Data (transfer syntaxes 1.2.840.10008.1.2.4.57 and .70: ITU-T T.81 process 14, Huffman coding, one
+ * component) -> the same native little-endian frame buffer, for a batch of frames whose entropy-coded segments lie anywhere
+ * inside one device buffer.  The host reads each frame's markers (T.81 Annex B) and hands over, per frame:
+ *   d_scan_off / d_scan_len int64 [n_frames]: the bytes after the SOS header up to EOI or the fragment's end (any alignment);
+ *   d_params int32 [n_frames][4]: the precision P (2 .. 16, at most 8 * bytes_per_sample), the selection value Ss (1 .. 7),
+ *   the point transform Pt (< P), the restart interval in samples (0: none; a whole number of rows, T.81 H.1.1);
+ *   d_huff uint8 [n_frames][33]: BITS[16] then HUFFVAL[17] of the table SOS selects (unused values 0xFF).
+ * One wave decodes one frame in one launch (T.81 Annex H, F.2.2): FF 00 gives the data byte FF, a marker ends the data; a
+ * token is a canonical-Huffman code of 1 .. 16 bits for the category SSSS (0 .. 16) and SSSS extra bits -- category 0 the
+ * difference 0, category 16 the difference 32768 with NO extra bits, a value with a leading zero bit v - (2^SSSS - 1).  The
+ * sample is (Px + difference) mod 2^16, stored shifted left by Pt and zero-extended into d_native
+ * [n_frames][rows * cols * bytes_per_sample]; with Ra left, Rb above, Rc above-left (the values before the shift) Px is
+ * 1 Ra, 2 Rb, 3 Rc, 4 Ra + Rb - Rc, 5 Ra + ((Rb - Rc) >> 1), 6 Rb + ((Ra - Rc) >> 1), 7 (Ra + Rb) >> 1 (H.1.2.1); the first
+ * sample of the scan and of every restart interval is predicted by 2^(P - Pt - 1), the rest of that row by Ra, the first
+ * column of every other row by Rb.  At an interval's end the bits up to the byte boundary are dropped, FF D0 + (k mod 8)
+ * must follow and the prediction starts over; the intervals of a frame are one chain (they are not decoded in parallel).
+ *   d_status int32 [n_frames] (zeroed here), per frame: bit 0 the window does not lie inside [0, nbytes) or a parameter or
+ *   the table is unsound (nothing of that frame is read or stored), bit 1 the data ends before rows * cols samples (a marker
+ *   other than the expected RSTn, or the window's end), bit 2 corrupt data (a code that is not in the table, a wrong restart
+ *   index, data where a restart marker belongs).  A flagged frame may be partly written; no other frame is touched.  Bytes
+ *   after the last sample are not looked at.
+ *   d_work: pl_dicom_jpegll_work_bytes() bytes (-1 for arguments pl_dicom_jpegll_decode refuses; 0 today -- both rows the
+ *   prediction needs are buffered in LDS -- and the pointer may then be null).
+ * bytes_per_sample 1 / 2 and cols <= PL_DICOM_JPEGLL_MAX_COLS (else unsupported); 1 <= n_frames <= 65535, rows, cols >= 1,
+ * non-null pointers (else invalid argument): checked before any launch. */
+#define PL_DICOM_JPEGLL_MAX_COLS 8192
+int64_t pl_dicom_jpegll_work_bytes(int64_t n_frames, int rows, int cols);
+int pl_dicom_jpegll_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_scan_off, const int64_t* d_scan_len,
+                           const int32_t* d_params, const unsigned char* d_huff, int64_t n_frames, int rows, int cols,
+                           int bytes_per_sample, unsigned char* d_native, int32_t* d_status, void* d_work, void* stream);
 
 /* ---- f1 ("next" row), the TIFF half: strip TIFFs of scanned film -> typed frames ----------------------------------
  * `np.asarray(PIL.Image.open(f))` (libtiff) for a STACK of classic strip TIFFs of one width, height, BitsPerSample and

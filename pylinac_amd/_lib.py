@@ -174,6 +174,8 @@ SIGNATURES = {
     "pl_dicom_decode": ([_p, _l, _p, _l, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _d, _d, _p, _p], C.c_int),
     "pl_dicom_rle_work_bytes": ([_l, _i, _l], C.c_int64),
     "pl_dicom_rle_decode": ([_p, _l, _p, _p, _l, _i, _l, _i, _i, _p, _p, _p, _p], C.c_int),
+    "pl_dicom_jpegll_work_bytes": ([_l, _i, _i], C.c_int64),
+    "pl_dicom_jpegll_decode": ([_p, _l, _p, _p, _p, _p, _l, _i, _i, _i, _p, _p, _p, _p], C.c_int),
     "pl_tiff_work_bytes": ([_l, _l, _l, _i, _i, _i, _i, _i], C.c_int64),
     "pl_tiff_decode": ([_p, _l, _p, _p, _p, _l, _l, _p, _l, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p], C.c_int),
     "pl_tiff_work_bytes_ex": ([_l, _l, _l, _i, _i, _i, _i, _i], C.c_int64),

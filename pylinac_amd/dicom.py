@@ -21,6 +21,12 @@ native little-endian frame buffer, and ``pl_dicom_decode`` takes that buffer whe
 unused-bit correction is asked for.  ``metadata.PixelDataFragments`` (our name, not pydicom's) lists the fragments as
 (offset, length).  The other compressed (encapsulated) transfer syntaxes and deflate belong to pydicom's codec plug-ins and
 reader, not to this path: ``NotImplementedError``.
+
+With ``jpeg_lossless=True`` (``read_part10``, ``load_frames``, ``DicomImage``) the two JPEG Lossless syntaxes
+(1.2.840.10008.1.2.4.57 and .70: T.81 process 14, Huffman coding, one component) are decoded too: the host reads every frame's
+markers (``_jpegll_header``), the frames' payloads go to the device compressed and ``pl_dicom_jpegll_decode``
+(``decode_jpeg_lossless_frames``: one wave per frame, one launch, nothing read back) writes the same native buffer.  Without
+the keyword they are refused as before.
 """
 from __future__ import annotations
 
@@ -45,6 +51,8 @@ RLE_LOSSLESS = "1.2.840.10008.1.2.5"
 RLE_CHUNK = 1024                                             # PL_DICOM_RLE_CHUNK: input bytes per chunk of the three passes
 _RLE_SHORT = "The amount of decoded RLE segment data doesn't match the expected amount"
 _RLE_PADDING = "The decoded RLE segment contains non-conformant padding"
+JPEG_LOSSLESS = ("1.2.840.10008.1.2.4.57", "1.2.840.10008.1.2.4.70")   # T.81 process 14: any predictor / first-order prediction
+JPEGLL_MAX_COLS = 8192                                       # PL_DICOM_JPEGLL_MAX_COLS: the rows the kernel buffers in LDS
 _LONG_VRS = {b"OB", b"OD", b"OF", b"OL", b"OV", b"OW", b"SQ", b"UC", b"UN", b"UR", b"UT", b"SV", b"UV"}
 
 # (group, element) -> (keyword, VR): the elements the image classes read (the VR column serves implicit-VR streams)
@@ -134,10 +142,12 @@ def _skip_undefined(buf: memoryview, pos: int, explicit: bool, big: bool) -> int
             pos, _, _, _, _ = _element(buf, pos, explicit, big)
 
 
-def _fragments(buf: memoryview, pos: int, out: list) -> int:
+def _fragments(buf: memoryview, pos: int, out: list, frame_table: list | None = None) -> int:
     """The items of an encapsulated Pixel Data value starting at ``pos`` (PS3.5 section A.4): the Basic Offset Table, then one
     item per fragment, closed by (FFFE,E0DD) -> the position after the delimiter; ``out`` receives (offset, length) of every
-    fragment.  A filled Basic Offset Table must agree with the walk (RLE: one fragment per frame, section A.4.2)."""
+    fragment.  A filled Basic Offset Table must agree with the walk (RLE: one fragment per frame, section A.4.2).
+    ``frame_table`` (JPEG Lossless: a frame may span fragments): a list that receives the table, whose entries must then
+    start at 0, increase and each name the item tag of a fragment."""
     n, table, tags = len(buf), None, []
     while True:
         if pos + 8 > n:
@@ -157,14 +167,21 @@ def _fragments(buf: memoryview, pos: int, out: list) -> int:
         pos += 8 + ln
     if table is None:
         raise ValueError("malformed encapsulated Pixel Data: the Basic Offset Table item is missing")
-    if table and table != [t - tags[0] for t in tags]:
+    starts = [t - tags[0] for t in tags]
+    if frame_table is None:
+        agrees = not table or table == starts
+    else:
+        agrees = not table or (table[0] == 0 and all(b > a for a, b in zip(table, table[1:])) and set(table) <= set(starts))
+        frame_table.extend(table)
+    if not agrees:
         raise ValueError("malformed encapsulated Pixel Data: the Basic Offset Table disagrees with the fragments that follow it")
     return pos + 8
 
 
-def _element(buf: memoryview, pos: int, explicit: bool, big: bool, fragments: list | None = None):
+def _element(buf: memoryview, pos: int, explicit: bool, big: bool, fragments: list | None = None, frame_table: list | None = None):
     """One data element at ``pos`` -> (position after it, (group, element), VR or None, value offset, value length).
-    ``fragments``: a list that receives the fragments of an encapsulated (7FE0,0010) -- RLE Lossless; None refuses them."""
+    ``fragments``: a list that receives the fragments of an encapsulated (7FE0,0010) -- RLE Lossless, JPEG Lossless with
+    ``frame_table`` (``_fragments``); None refuses them."""
     e = ">" if big else "<"
     g, el = struct.unpack_from(e + "HH", buf, pos)
     pos += 4
@@ -185,17 +202,19 @@ def _element(buf: memoryview, pos: int, explicit: bool, big: bool, fragments: li
     if ln == 0xFFFFFFFF:
         if (g, el) == (0x7FE0, 0x0010):
             if fragments is not None:
-                return _fragments(buf, pos, fragments), (g, el), vr, start, -1
+                return _fragments(buf, pos, fragments, frame_table), (g, el), vr, start, -1
             raise NotImplementedError("encapsulated (compressed) Pixel Data: decoded by pydicom's codec plug-ins, not by this path")
         return _skip_undefined(buf, pos, explicit, big), (g, el), vr, start, -1
     return pos + ln, (g, el), vr, start, ln
 
 
-def read_part10(source) -> tuple[Metadata, np.ndarray]:
+def read_part10(source, jpeg_lossless: bool = False) -> tuple[Metadata, np.ndarray]:
     """``pydicom.dcmread(source, force=True)`` as far as the image classes need it -> (metadata, the file's bytes as a uint8
     array).  ``metadata.PixelData`` (``FloatPixelData`` / ``DoubleFloatPixelData``) is the pair (offset, length) of the value
     inside those bytes -- the samples are never copied on the host.  RLE Lossless: ``PixelData`` is (offset, -1) and
-    ``metadata.PixelDataFragments`` the list of (offset, length) of the fragments."""
+    ``metadata.PixelDataFragments`` the list of (offset, length) of the fragments.  ``jpeg_lossless=True`` walks the items of
+    the two JPEG Lossless syntaxes (``JPEG_LOSSLESS``) the same way; ``metadata.PixelDataOffsetTable`` is then the Basic
+    Offset Table (a list, empty or one entry per frame).  Without it they are refused like every other encapsulated syntax."""
     if isinstance(source, (bytes, bytearray, memoryview, np.ndarray)):
         data = np.frombuffer(bytes(source) if not isinstance(source, np.ndarray) else source.tobytes(), dtype=np.uint8)
     elif isinstance(source, (str, Path)):
@@ -204,14 +223,14 @@ def read_part10(source) -> tuple[Metadata, np.ndarray]:
         if isinstance(source, io.IOBase) or hasattr(source, "seek"):
             source.seek(0)
         data = np.frombuffer(source.read(), dtype=np.uint8)
-    return _walk_part10(memoryview(data).cast("B")), data
+    return _walk_part10(memoryview(data).cast("B"), jpeg_lossless=jpeg_lossless), data
 
 
 class _PrefixTooShort(Exception):
     """the prefix of a member ends before its (7FE0,0010) element header"""
 
 
-def _walk_part10(buf: memoryview, size: int | None = None) -> Metadata:
+def _walk_part10(buf: memoryview, size: int | None = None, jpeg_lossless: bool = False) -> Metadata:
     """The element walk of ``read_part10`` over ``buf``.  ``size`` None: ``buf`` is the whole file.  Otherwise the PREFIX form
     ``load_zip`` uses: ``buf`` holds the first bytes of a file of ``size`` bytes, the walk stops at the Pixel Data element
     header -- (offset, length) of its value are validated against ``size``, not against the prefix -- and raises
@@ -219,14 +238,14 @@ def _walk_part10(buf: memoryview, size: int | None = None) -> Metadata:
     n = len(buf)
     whole = size is None or n >= size
     try:
-        return _walk_elements(buf, n, size, whole)
+        return _walk_elements(buf, n, size, whole, jpeg_lossless)
     except struct.error:
         if whole:
             raise
         raise _PrefixTooShort from None
 
 
-def _walk_elements(buf: memoryview, n: int, size, whole: bool) -> Metadata:
+def _walk_elements(buf: memoryview, n: int, size, whole: bool, jpeg_lossless: bool = False) -> Metadata:
     pos = 132 if n >= 132 and bytes(buf[128:132]) == b"DICM" else 0
     values: dict = {}
     ts = IMPLICIT_LE if pos == 0 else EXPLICIT_LE          # (no preamble, force=True: pydicom assumes implicit VR little endian)
@@ -247,9 +266,11 @@ def _walk_elements(buf: memoryview, n: int, size, whole: bool) -> Metadata:
     if size is not None and ts == RLE_LOSSLESS:
         raise NotImplementedError("RLE Lossless Pixel Data inside an archive: the segment headers lie inside the compressed part; "
                                   "extract the member and use load_frames")
-    fragments = [] if ts == RLE_LOSSLESS else None
+    jpegll = jpeg_lossless and size is None and ts in JPEG_LOSSLESS
+    fragments = [] if ts == RLE_LOSSLESS or jpegll else None
+    frame_table = [] if jpegll else None
     while pos + 8 <= n:
-        pos, tag, vr, start, ln = _element(buf, pos, explicit, big, fragments)
+        pos, tag, vr, start, ln = _element(buf, pos, explicit, big, fragments, frame_table)
         if size is not None and tag == (0x7FE0, 0x0010):    # the prefix form ends here: the value is judged against the file
             if start > size or ln > size - start:
                 raise ValueError(f"the Pixel Data value ({ln} bytes at offset {start}) lies outside the file ({size} bytes)")
@@ -259,6 +280,8 @@ def _walk_elements(buf: memoryview, n: int, size, whole: bool) -> Metadata:
             raise _PrefixTooShort
         if tag == (0x7FE0, 0x0010) and ln < 0:
             values["PixelData"], values["PixelDataFragments"] = (start, -1), fragments
+            if jpegll:
+                values["PixelDataOffsetTable"] = frame_table
         if tag not in _TAGS or ln < 0:
             continue
         key, table_vr = _TAGS[tag]
@@ -407,6 +430,201 @@ def _check_rle_status(status: torch.Tensor, owner, names) -> None:
         warnings.warn(f"{_RLE_PADDING} ({names[owner[int(np.flatnonzero(flags & 4)[0])]]})")
 
 
+def _jpegll_cols(cols: int) -> None:
+    if cols > JPEGLL_MAX_COLS:
+        raise ValueError(f"JPEG Lossless frames of {cols} columns: the device decode buffers rows of at most {JPEGLL_MAX_COLS} samples")
+
+
+def decode_jpeg_lossless_frames(file_bytes, scan_off, scan_len, params, huff, rows: int, cols: int, bits_allocated: int,
+                                bits_stored: int | None = None, pixel_representation: int = 0, correct_unused_bits: bool = False,
+                                out: str = "container", rescale=None, device=None,
+                                native: torch.Tensor | None = None) -> torch.Tensor:
+    """``pl_dicom_jpegll_decode``, the JPEG Lossless counterpart of ``decode_rle_frames`` (T.81 process 14, Annex H): N frames
+    whose entropy-coded segments lie anywhere inside ``file_bytes`` (uint8 array / tensor; device tensors are used in place).
+    ``scan_off`` / ``scan_len`` int64 [N]: the bytes after each frame's SOS header, up to EOI or the fragment's end;
+    ``params`` int32 [N, 4]: precision, selection value, point transform, restart interval in samples (0: none); ``huff``
+    uint8 [N, 33]: BITS[16] then HUFFVAL[17] of the table SOS selects.  One wave decodes one frame.  -> device tensor
+    [N, rows, cols] exactly as ``decode_frames`` gives it for the same samples stored native, zero-extended into the
+    container (``out``, ``rescale``, ``correct_unused_bits``: the decoded little-endian buffer goes through
+    ``pl_dicom_decode``; the plain container dtype IS that buffer, returned as a view).  ``_pl_status`` int32 [N]: bit 0 a
+    window outside the buffer or an unsound parameter (the frame is left untouched), bit 1 the data ends before rows * cols
+    samples, bit 2 corrupt data (a code outside the table, a wrong restart marker).  ``native``: a uint8 device tensor
+    [N, rows * cols * BitsAllocated / 8] to decode into.  ``ValueError`` for more than ``JPEGLL_MAX_COLS`` columns."""
+    _jpegll_cols(cols)
+    dev = on_device(device)
+    bits, rep = int(bits_allocated), int(pixel_representation)
+    if bits not in (8, 16):
+        raise ValueError("decode_jpeg_lossless_frames: BitsAllocated 8 or 16")
+    cont = {(8, 0): torch.uint8, (8, 1): torch.int8, (16, 0): torch.uint16, (16, 1): torch.int16}[(bits, rep)]
+    buf = bytes_tensor(file_bytes, dev)
+    so, sl = index_tensor(scan_off, torch.int64, dev).reshape(-1), index_tensor(scan_len, torch.int64, dev).reshape(-1)
+    n = int(so.numel())
+    par = index_tensor(params, torch.int32, dev).reshape(-1, 4)
+    tab = bytes_tensor(huff, dev).reshape(-1, 33)
+    if not (sl.numel() == par.shape[0] == tab.shape[0] == n):
+        raise ValueError("decode_jpeg_lossless_frames: scan_off and scan_len [N], params [N, 4] and huff [N, 33] must agree in N")
+    frame_bytes = rows * cols * (bits // 8)
+    if native is None:
+        native = torch.empty((n, frame_bytes), dtype=torch.uint8, device=dev)
+    elif native.dtype != torch.uint8 or tuple(native.shape) != (n, frame_bytes) or not native.is_contiguous() or not native.is_cuda:
+        raise ValueError("decode_jpeg_lossless_frames: native must be a contiguous uint8 device tensor "
+                         "[N, rows * cols * BitsAllocated / 8]")
+    lib = _lib.load()
+    nwork = int(lib.pl_dicom_jpegll_work_bytes(n, rows, cols))
+    work = torch.empty(max(nwork, 16), dtype=torch.uint8, device=dev)
+    status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    check(lib.pl_dicom_jpegll_decode(buf.data_ptr(), buf.numel(), so.data_ptr(), sl.data_ptr(), par.data_ptr(), tab.data_ptr(), n,
+                                     rows, cols, bits // 8, native.data_ptr(), status.data_ptr(), work.data_ptr(),
+                                     torch.cuda.current_stream(dev).cuda_stream), "pl_dicom_jpegll_decode")
+    stored = bits if bits_stored is None else int(bits_stored)
+    if out == "container" and not (correct_unused_bits and stored < bits):
+        res = native.view(cont).reshape(n, rows, cols)
+    else:
+        res = decode_frames(native.reshape(-1), torch.arange(n, dtype=torch.int64, device=dev) * frame_bytes, rows, cols, bits,
+                            stored, rep, big_endian=False, correct_unused_bits=correct_unused_bits, out=out, rescale=rescale,
+                            device=dev)
+    res._pl_status = status[:n]
+    return res
+
+
+_SOF_REFUSED = {0xC0: "SOF0 (baseline DCT)", 0xC1: "SOF1 (extended sequential DCT)", 0xC2: "SOF2 (progressive DCT)",
+                0xC5: "SOF5 (differential sequential DCT)", 0xC6: "SOF6 (differential progressive DCT)",
+                0xC7: "SOF7 (differential lossless)", 0xC8: "JPG (reserved)", 0xC9: "SOF9 (arithmetic coding)",
+                0xCA: "SOF10 (arithmetic coding)", 0xCB: "SOF11 (lossless, arithmetic coding)",
+                0xCD: "SOF13 (arithmetic coding)", 0xCE: "SOF14 (arithmetic coding)", 0xCF: "SOF15 (arithmetic coding)",
+                0xCC: "DAC (arithmetic conditioning)", 0xDC: "DNL (number of lines)", 0xDE: "DHP (hierarchical)",
+                0xDF: "EXP (hierarchical)"}
+
+
+def _jpegll_header(data, rows: int, cols: int, bits: int, name: str):
+    """The markers of one frame's JPEG stream up to its scan (T.81 Annex B) -> (offset of the entropy-coded segment inside
+    ``data``, its length up to the end of ``data``, [P, selection value, Pt, restart interval], the 33 bytes BITS + HUFFVAL
+    of the table SOS selects).  Every offset is checked against ``data``.  ``NotImplementedError`` for a process other than
+    Huffman-coded lossless (any SOFn but SOF3, DAC, DNL, hierarchical markers) and for more than one component;
+    ``ValueError`` for a malformed stream."""
+    data = bytes(data)
+    n = len(data)
+    if n < 2 or data[:2] != b"\xff\xd8":
+        raise ValueError(f"{name}: the JPEG stream does not start with SOI")
+    pos, tables, interval, frame = 2, {}, 0, None
+    while True:
+        while pos + 1 < n and data[pos] == 0xFF and data[pos + 1] == 0xFF:         # fill bytes before a marker (B.1.1.2)
+            pos += 1
+        if pos + 2 > n:
+            raise ValueError(f"{name}: the JPEG stream ends without SOS (no scan)")
+        if data[pos] != 0xFF:
+            raise ValueError(f"{name}: a JPEG marker was expected at byte {pos} of the frame")
+        m = data[pos + 1]
+        if m == 0xD9:
+            raise ValueError(f"{name}: EOI without SOS (no scan)")
+        if m == 0x01 or 0xD0 <= m <= 0xD8:                                          # stand-alone markers
+            pos += 2
+            continue
+        if pos + 4 > n:
+            raise ValueError(f"{name}: the JPEG stream ends without SOS (no scan)")
+        ln = struct.unpack_from(">H", data, pos + 2)[0]
+        if ln < 2 or pos + 2 + ln > n:
+            raise ValueError(f"{name}: the segment of marker FF{m:02X} lies outside the fragment")
+        seg = data[pos + 4:pos + 2 + ln]
+        if m in _SOF_REFUSED:
+            raise NotImplementedError(f"{name}: {_SOF_REFUSED[m]}, marker FF{m:02X}: only Huffman-coded lossless JPEG (SOF3) "
+                                      "is decoded by this path")
+        if m == 0xC3:
+            if len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
+                raise ValueError(f"{name}: malformed SOF3 segment")
+            p, y, x, nf = seg[0], struct.unpack_from(">H", seg, 1)[0], struct.unpack_from(">H", seg, 3)[0], seg[5]
+            if nf != 1:
+                raise NotImplementedError(f"{name}: SOF3 with Nf = {nf} components: single-component frames only")
+            if y == 0:
+                raise NotImplementedError(f"{name}: SOF3 with Y = 0 leaves the number of lines to a DNL marker")
+            if not 2 <= p <= 16:
+                raise ValueError(f"{name}: SOF3 precision {p} (2 .. 16)")
+            if p > bits:
+                raise ValueError(f"{name}: SOF3 precision {p} exceeds BitsAllocated = {bits}")
+            if (y, x) != (rows, cols):
+                raise ValueError(f"{name}: SOF3 states Y x X = {y} x {x} where Rows x Columns = {rows} x {cols}")
+            frame = (p, seg[6])
+        elif m == 0xC4:
+            at = 0
+            while at < len(seg):
+                if at + 17 > len(seg):
+                    raise ValueError(f"{name}: a DHT table definition is cut off")
+                tc, th = seg[at] >> 4, seg[at] & 15
+                counts = seg[at + 1:at + 17]
+                total = sum(counts)
+                if tc != 0 or th > 3:
+                    raise ValueError(f"{name}: DHT table class {tc}, id {th}: lossless scans use class 0, ids 0 .. 3")
+                if total > 17:
+                    raise ValueError(f"{name}: a DHT table of {total} symbols (at most 17 categories, 0 .. 16)")
+                if at + 17 + total > len(seg):
+                    raise ValueError(f"{name}: a DHT table definition is cut off")
+                values = seg[at + 17:at + 17 + total]
+                if any(v > 16 for v in values):
+                    raise ValueError(f"{name}: a DHT table holds the symbol {max(values)} (categories 0 .. 16)")
+                if sum(c << (15 - k) for k, c in enumerate(counts)) > 1 << 16:
+                    raise ValueError(f"{name}: a DHT table is over-subscribed (Kraft sum above 1)")
+                tables[th] = bytes(counts) + values + b"\xff" * (17 - total)     # (a later definition replaces the earlier)
+                at += 17 + total
+        elif m == 0xDD:
+            if ln != 4:
+                raise ValueError(f"{name}: malformed DRI segment")
+            interval = struct.unpack_from(">H", seg, 0)[0]
+        elif m == 0xDA:
+            if frame is None:
+                raise ValueError(f"{name}: SOS before SOF3")
+            if len(seg) < 1 or seg[0] != 1 or len(seg) != 6:
+                raise ValueError(f"{name}: SOS with Ns = {seg[0] if seg else '?'}: one component per scan")
+            cs, td, ss, ah, al = seg[1], seg[2] >> 4, seg[3], seg[5] >> 4, seg[5] & 15
+            if cs != frame[1]:
+                raise ValueError(f"{name}: SOS selects component {cs}, SOF3 defines {frame[1]}")
+            if not 1 <= ss <= 7:
+                raise ValueError(f"{name}: SOS selection value {ss} (lossless predictors 1 .. 7)")
+            if ah != 0 or al >= frame[0]:
+                raise ValueError(f"{name}: SOS with Ah = {ah}, point transform {al} at precision {frame[0]}")
+            if td not in tables:
+                raise ValueError(f"{name}: SOS selects the Huffman table {td}, which no DHT defines")
+            if interval % cols:
+                raise ValueError(f"{name}: the restart interval {interval} is not a whole number of rows of {cols} samples "
+                                 "(T.81 H.1.1)")
+            start = pos + 2 + ln
+            return start, n - start, [frame[0], ss, al, interval], tables[td]
+        pos += 2 + ln                                                               # APPn, COM, DQT, ...: skipped
+
+
+def _jpegll_frames(meta: Metadata, frames: int, name: str) -> list:
+    """The fragments of each frame of a JPEG Lossless file (PS3.5 section A.4, a frame may span fragments): one frame with an
+    empty Basic Offset Table owns them all, a filled table says where frames begin, and as many fragments as frames are one
+    each -> [[(offset, length), ...] per frame]; ``ValueError`` otherwise."""
+    found, table = meta.PixelDataFragments, meta.PixelDataOffsetTable
+    if table:
+        if len(table) != frames or not found:
+            raise ValueError(f"{name}: a Basic Offset Table of {len(table)} entries for NumberOfFrames = {frames}")
+        first = found[0][0]
+        begins = [k for k, (o, _) in enumerate(found) if o - first in set(table)] + [len(found)]
+        return [found[a:b] for a, b in zip(begins, begins[1:])]
+    if frames == 1 and found:
+        return [list(found)]
+    if len(found) == frames:
+        return [[f] for f in found]
+    raise ValueError(f"{name}: {len(found)} JPEG fragments for NumberOfFrames = {frames} with an empty Basic Offset Table "
+                     "(one fragment per frame, or a filled table)")
+
+
+_JPEGLL_FLAGS = ((1, "the scan window or a parameter is unsound"), (2, "the data ends before Rows x Columns samples"),
+                 (4, "corrupt data (a code outside the Huffman table or a wrong restart marker)"))
+
+
+def _check_jpegll_status(status: torch.Tensor, owner, names) -> None:
+    """``ValueError`` naming the file and the frame for the first flagged frame of ``decode_jpeg_lossless_frames`` (one
+    transfer)."""
+    flags = status.cpu().numpy()
+    bad = np.flatnonzero(flags)
+    if bad.size:
+        k = int(bad[0])
+        why = "; ".join(text for bit, text in _JPEGLL_FLAGS if flags[k] & bit)
+        raise ValueError(f"{names[owner[k]]}, frame {k} of the stack: JPEG Lossless Pixel Data: {why}")
+
+
 def _check_status(frames: torch.Tensor) -> torch.Tensor:
     st = getattr(frames, "_pl_status", None)
     if st is not None and bool(st.any()):
@@ -416,17 +634,23 @@ def _check_status(frames: torch.Tensor) -> torch.Tensor:
 
 
 def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bool | None = None,
-                correct_unused_bits: bool = False, device=None, check: bool = True):
+                correct_unused_bits: bool = False, device=None, check: bool = True, jpeg_lossless: bool = False):
     """The batched loader: Part-10 files (paths, bytes or file objects; every file may hold several frames) of ONE pixel
     format, frame size and kind (all native or all RLE Lossless) -> (device tensor [N, H, W], list of per-file metadata).  Per
     file exactly what ``DicomImage.__init__`` does (image.py:1431-1444): ``pixel_array`` [``.astype(dtype)``] then
     ``_rescale_dicom_values``;
     files with both rescale tags take the fused float64 form of the kernel when every file carries the SAME slope and
-    intercept (a series), otherwise the frames are decoded once and rescaled file by file."""
+    intercept (a series), otherwise the frames are decoded once and rescaled file by file.
+
+    ``jpeg_lossless=True`` accepts a third kind: files of the JPEG Lossless syntaxes (``JPEG_LOSSLESS``: T.81 process 14,
+    SamplesPerPixel 1, BitsAllocated 8 or 16), decoded by ``decode_jpeg_lossless_frames`` with a wave per frame.  Their files
+    may differ in predictor, point transform, restart interval and Huffman table; a frame may span fragments (its payloads
+    are laid end to end on the host).  ``check=True`` reads the decode's status once and raises ``ValueError`` naming the
+    file and the frame."""
     sources = list(sources)
     metas, blobs = [], []
     for s in sources:
-        m, b = read_part10(s)
+        m, b = read_part10(s, jpeg_lossless=jpeg_lossless)
         metas.append(m)
         blobs.append(b)
     lay = [_layout(m) for m in metas]
@@ -434,11 +658,16 @@ def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bo
     for l in lay[1:]:
         if (l[0], l[4], l[5], l[6]) != (tdt, rows, cols, big):
             raise ValueError("load_frames: the files differ in pixel format or frame size (the reference's stacks refuse that too)")
+    names = [f"file {k}" + (f" ({s})" if isinstance(s, (str, Path)) else "") for k, s in enumerate(sources)]
+    kinds = {"jpegll" if "PixelDataOffsetTable" in m else "rle" if "PixelDataFragments" in m else "native" for m in metas}
+    if "jpegll" in kinds:
+        if len(kinds) > 1:
+            raise ValueError("load_frames: JPEG Lossless files are mixed with native or RLE Lossless files; load the kinds separately")
+        return _load_jpegll(metas, blobs, lay, names, dtype, raw_pixels, invert_pixels, correct_unused_bits, device, check), metas
     rle = ["PixelDataFragments" in m for m in metas]
     if any(rle) and not all(rle):
         raise ValueError("load_frames: native and RLE Lossless files are mixed; load the two kinds separately")
     rle = all(rle) and bool(metas)
-    names = [f"file {k}" + (f" ({s})" if isinstance(s, (str, Path)) else "") for k, s in enumerate(sources)]
     # one host buffer, every file at a 4-byte boundary; frame offsets (RLE: segment windows) inside it
     starts, offsets, owner, pos = [], [], [], 0
     for k, (b, l) in enumerate(zip(blobs, lay)):
@@ -490,6 +719,55 @@ def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bo
 
         verify = _check_status
     return _finish_frames(decode, verify, metas, owner, rows, cols, dtype, raw_pixels, invert_pixels, check), metas
+
+
+def _load_jpegll(metas, blobs, lay, names, dtype, raw_pixels: bool, invert_pixels, correct_unused_bits: bool, device, check: bool):
+    """``load_frames`` for JPEG Lossless files: every frame's fragment payloads end to end at a 4-byte boundary of one host
+    buffer (the kernel sees one window per frame), its markers parsed where they lie, then the tail every kind shares."""
+    _, _, ib, _, rows, cols, _, _ = lay[0]
+    host, tables, owner = _jpegll_stage(metas, blobs, lay, names)
+    stored = int(metas[0].get("BitsStored") or ib * 8)
+    common = dict(rows=rows, cols=cols, bits_allocated=ib * 8, bits_stored=stored,
+                  pixel_representation=int(metas[0].PixelRepresentation), correct_unused_bits=correct_unused_bits, device=device)
+    seen = []
+
+    def decode(**kw):
+        x = decode_jpeg_lossless_frames(host, *tables, **common, **kw)
+        seen.append(x._pl_status)                            # (an integer astype hands on a tensor without it)
+        return x
+
+    def verify(x):
+        _check_jpegll_status(seen[-1], owner, names)
+        return x
+
+    return _finish_frames(decode, verify, metas, owner, rows, cols, dtype, raw_pixels, invert_pixels, check)
+
+
+def _jpegll_stage(metas, blobs, lay, names):
+    """The host side of a JPEG Lossless stack -> (the staging buffer, (scan_off, scan_len, params, huff) as
+    ``decode_jpeg_lossless_frames`` takes them, the file of every frame); every refusal of a file happens here."""
+    _, _, ib, _, rows, cols, _, _ = lay[0]
+    if ib not in (1, 2):
+        raise NotImplementedError(f"JPEG Lossless Pixel Data with BitsAllocated {ib * 8}: 8 and 16 are decoded on the device")
+    _jpegll_cols(cols)
+    pieces, owner, scan_off, scan_len, params, huff, pos = [], [], [], [], [], [], 0
+    for k, (m, b, l) in enumerate(zip(metas, blobs, lay)):
+        for frags in _jpegll_frames(m, l[3], names[k]):
+            data = b[frags[0][0]:frags[0][0] + frags[0][1]] if len(frags) == 1 else np.concatenate([b[o:o + n] for o, n in frags])
+            start, length, par, table = _jpegll_header(data, rows, cols, ib * 8, names[k])
+            pieces.append((pos, data))
+            owner.append(k)
+            scan_off.append(pos + start)
+            scan_len.append(length)
+            params.append(par)
+            huff.append(np.frombuffer(table, dtype=np.uint8))
+            pos += (len(data) + 3) & ~3
+    host = np.zeros(pos, dtype=np.uint8)
+    for at, data in pieces:
+        host[at:at + len(data)] = data
+    tables = (np.asarray(scan_off, dtype=np.int64), np.asarray(scan_len, dtype=np.int64), np.asarray(params, dtype=np.int32),
+              np.stack(huff))
+    return host, tables, owner
 
 
 def _finish_frames(decode, verify, metas, owner, rows: int, cols: int, dtype, raw_pixels: bool, invert_pixels, check: bool):
@@ -678,11 +956,12 @@ class DicomImage(_image_base()):
     class-API image; ``metadata`` answers the tags the reference's properties read."""
 
     def __init__(self, path, *, dtype=None, dpi: float = None, sid: float = None, sad: float = 1000, raw_pixels: bool = False,
-                 invert_pixels: bool | None = None):
+                 invert_pixels: bool | None = None, jpeg_lossless: bool = False):
         self.path = path
         self._sid, self._dpi, self._sad = sid, dpi, sad
         self._raw_pixels, self._invert_pixels = raw_pixels, invert_pixels
-        frames, metas = load_frames([path], dtype=dtype, raw_pixels=raw_pixels, invert_pixels=invert_pixels)
+        frames, metas = load_frames([path], dtype=dtype, raw_pixels=raw_pixels, invert_pixels=invert_pixels,
+                                    jpeg_lossless=jpeg_lossless)
         self.metadata = metas[0]
         tdt = _layout(self.metadata)[0]
         self._original_dtype = np.dtype(str(tdt).replace("torch.", ""))
