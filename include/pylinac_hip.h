@@ -602,6 +602,56 @@ int pl_dicom_jpegll_decode(const unsigned char* d_bytes, int64_t nbytes, const i
                            const int32_t* d_params, const unsigned char* d_huff, int64_t n_frames, int rows, int cols,
                            int bytes_per_sample, unsigned char* d_native, int32_t* d_status, void* d_work, void* stream);
 
+/* Encapsulated Pixel Data that is already on the device (the members of a ZIP archive after pl_zip_extract): where the
+ * fragments lie, and a copy that lays fragments end to end.
+ * pl_dicom_encap_index walks the items of n_members encapsulated Pixel Data values (PS3.5 section A.4: the Basic Offset
+ * Table item, one item (FFFE,E000) per fragment, the Sequence Delimitation Item (FFFE,E0DD)), one wave per value, all values
+ * side by side in one launch.  Value m: its first item starts at byte d_first[m] of d_bytes, and nothing at or beyond byte
+ * d_end[m] (the end of the file that holds it) belongs to it; any alignment.  The results go to ONE block d_result of
+ * pl_dicom_encap_index_bytes() bytes on a 16-byte boundary, so that the host reads them in one transfer; with
+ * H = head_bytes its parts follow each other in this order:
+ *   int64  frag [n_members][cap][3]   payload offset, length, offset of the item's tag (all from the start of d_bytes);
+ *   uint8  head [n_members][cap][H]   the first min(length, H) bytes of the fragment, zeros behind them;
+ *   int32  info [n_members][4]        status, fragments found, Basic Offset Table entries found, 0;
+ *   uint32 table[n_members][tcap]     the Basic Offset Table;
+ * padded to a multiple of 16 bytes.  Fragments and table entries are COUNTED in full; only the first cap / tcap of them are
+ * stored, and nothing beyond a member's slots is written.  Status bits:
+ *   PL_ENCAP_DESCRIPTOR  the window [d_first, d_end) does not lie inside [0, nbytes]: nothing is read, only the status word
+ *                        of that member is stored;
+ *   PL_ENCAP_MALFORMED   the walk stopped at an item that is none: a tag other than the two above, an undefined length or a
+ *                        length that reaches beyond d_end -- with PL_ENCAP_NO_DELIMITER: fewer than 8 bytes were left
+ *                        before d_end and the delimiter had not come;
+ *   PL_ENCAP_TABLE       the delimiter came before any item (no table item) -- with PL_ENCAP_TABLE_LENGTH: the first item's
+ *                        length is no multiple of 4;
+ *   PL_ENCAP_CAPACITY    more fragments than cap or more table entries than tcap: what lies within the capacities is valid.
+ * What was stored before the walk stopped is valid, the counts included.  Every read lies inside the member's window; a
+ * length is compared with what is left of the window before the walk passes it.
+ *   1 <= n_members < 2^31, 1 <= cap, tcap <= 2^24, head_bytes a multiple of 16 from 16 to PL_DICOM_ENCAP_MAX_HEAD, nbytes >= 0,
+ *   non-null pointers, d_result on a 16-byte boundary (else invalid argument; pl_dicom_encap_index_bytes: -1): checked
+ *   before any launch.  No work memory.
+ * pl_copy_ranges copies n_ranges byte ranges between two device buffers: range r is the d_len[r] bytes at byte
+ * d_src_off[r] of d_src, they go to byte d_dst_off[r] of d_dst; any alignment on either side.  16-byte stores on 16-byte
+ * boundaries fed by 4-dword loads on dword boundaries that are funnel-shifted by the misalignment of the two sides; the bytes in front of and behind the aligned
+ * blocks are copied one by one, so no byte outside a destination range is written.  d_status int32 [n_ranges]: 1 for a
+ * range that does not lie inside both buffers (nothing of it is copied), else 0.  Destination ranges that overlap are the
+ * caller's error.  max_len: an upper bound of d_len (it shapes the grid only).  One launch, nothing read back, no work
+ * memory.  1 <= n_ranges < 2^31, sizes >= 0, non-null pointers, d_src and d_dst on 4-byte boundaries (else invalid
+ * argument): checked before any launch. */
+#define PL_DICOM_ENCAP_HEAD 256
+#define PL_DICOM_ENCAP_MAX_HEAD 1024
+#define PL_ENCAP_DESCRIPTOR 1
+#define PL_ENCAP_MALFORMED 2
+#define PL_ENCAP_TABLE 4
+#define PL_ENCAP_CAPACITY 8
+#define PL_ENCAP_NO_DELIMITER 16
+#define PL_ENCAP_TABLE_LENGTH 32
+int64_t pl_dicom_encap_index_bytes(int64_t n_members, int cap, int tcap, int head_bytes);
+int pl_dicom_encap_index(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_first, const int64_t* d_end,
+                         int64_t n_members, int cap, int tcap, int head_bytes, unsigned char* d_result, void* stream);
+int pl_copy_ranges(const unsigned char* d_src, int64_t src_bytes, unsigned char* d_dst, int64_t dst_bytes,
+                   const int64_t* d_src_off, const int64_t* d_len, const int64_t* d_dst_off, int64_t n_ranges, int64_t max_len,
+                   int32_t* d_status, void* stream);
+
 /* ---- f1 ("next" row), the TIFF half: strip TIFFs of scanned film -> typed frames ----------------------------------
  * `np.asarray(PIL.Image.open(f))` (libtiff) for a STACK of classic strip TIFFs of one width, height, BitsPerSample and
  * SamplesPerPixel whose files lie anywhere inside one device buffer (copied as they are, compressed).  The host walks the

@@ -16,11 +16,13 @@
 // output) or 1 + 8 / BitsAllocated-bytes x (float64 output).
 #include "pl_common.h"
 
-// jpeg_lossless.hip is a translation unit of its own in the library; the CPU emulator of the tests builds a fixed list of
-// files that holds this one, so there it is compiled as a part of this file
+// jpeg_lossless.hip and dicom_encap.hip are translation units of their own in the library; the CPU emulator of the tests
+// builds a fixed list of files that holds this one, so there they are compiled as parts of this file
 #ifdef PL_HIPEMU
 #define PL_JPEGLL_IN_DICOM
 #include "jpeg_lossless.hip"
+#define PL_ENCAP_IN_DICOM
+#include "dicom_encap.hip"
 #endif
 
 namespace {

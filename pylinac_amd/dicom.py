@@ -27,6 +27,10 @@ With ``jpeg_lossless=True`` (``read_part10``, ``load_frames``, ``DicomImage``) t
 markers (``_jpegll_header``), the frames' payloads go to the device compressed and ``pl_dicom_jpegll_decode``
 (``decode_jpeg_lossless_frames``: one wave per frame, one launch, nothing read back) writes the same native buffer.  Without
 the keyword they are refused as before.
+
+``load_zip(encapsulated=True)`` reads both kinds out of ZIP archives: the members are inflated on the device, where
+``pl_dicom_encap_index`` (``index_encapsulated``) walks their items and hands the host every fragment's place and first bytes, and
+``pl_copy_ranges`` (``copy_ranges``) lays the fragments of a JPEG frame that spans several end to end.
 """
 from __future__ import annotations
 
@@ -34,6 +38,7 @@ import io
 import struct
 import warnings
 import zipfile
+from dataclasses import dataclass
 from pathlib import Path
 
 import numpy as np
@@ -151,37 +156,52 @@ def _fragments(buf: memoryview, pos: int, out: list, frame_table: list | None = 
     n, table, tags = len(buf), None, []
     while True:
         if pos + 8 > n:
-            raise ValueError("malformed encapsulated Pixel Data: the sequence delimiter is missing")
+            raise ValueError(_ITEMS_NO_DELIMITER)
         g, el, ln = struct.unpack_from("<HHI", buf, pos)
         if (g, el) == (0xFFFE, 0xE0DD):
             break
         if (g, el) != (0xFFFE, 0xE000) or ln == 0xFFFFFFFF or pos + 8 + ln > n:
-            raise ValueError("malformed encapsulated Pixel Data: an item of defined length inside the file was expected")
+            raise ValueError(_ITEMS_NO_ITEM)
         if table is None:
             if ln % 4:
-                raise ValueError("malformed encapsulated Pixel Data: the Basic Offset Table is no list of uint32 values")
+                raise ValueError(_ITEMS_TABLE_LENGTH)
             table = list(struct.unpack_from(f"<{ln // 4}I", buf, pos + 8))
         else:
             tags.append(pos)
             out.append((pos + 8, ln))
         pos += 8 + ln
     if table is None:
-        raise ValueError("malformed encapsulated Pixel Data: the Basic Offset Table item is missing")
+        raise ValueError(_ITEMS_NO_TABLE)
+    _check_offset_table(table, tags, frame_table is not None)
+    if frame_table is not None:
+        frame_table.extend(table)
+    return pos + 8
+
+
+_ITEMS = "malformed encapsulated Pixel Data: "
+_ITEMS_NO_DELIMITER = _ITEMS + "the sequence delimiter is missing"
+_ITEMS_NO_ITEM = _ITEMS + "an item of defined length inside the file was expected"
+_ITEMS_TABLE_LENGTH = _ITEMS + "the Basic Offset Table is no list of uint32 values"
+_ITEMS_NO_TABLE = _ITEMS + "the Basic Offset Table item is missing"
+_HEADER_ONLY = object()         # ``_element(fragments=...)``: stop at the header of an encapsulated (7FE0,0010), walk no item
+
+
+def _check_offset_table(table: list, tags: list, frames_span: bool) -> None:
+    """A filled Basic Offset Table against the item tags found (``_fragments``): RLE, one fragment per frame -- the table IS
+    the tags' offsets from the first; ``frames_span`` (JPEG Lossless) -- it starts at 0, increases and names item tags."""
     starts = [t - tags[0] for t in tags]
-    if frame_table is None:
+    if not frames_span:
         agrees = not table or table == starts
     else:
         agrees = not table or (table[0] == 0 and all(b > a for a, b in zip(table, table[1:])) and set(table) <= set(starts))
-        frame_table.extend(table)
     if not agrees:
-        raise ValueError("malformed encapsulated Pixel Data: the Basic Offset Table disagrees with the fragments that follow it")
-    return pos + 8
+        raise ValueError(_ITEMS + "the Basic Offset Table disagrees with the fragments that follow it")
 
 
 def _element(buf: memoryview, pos: int, explicit: bool, big: bool, fragments: list | None = None, frame_table: list | None = None):
     """One data element at ``pos`` -> (position after it, (group, element), VR or None, value offset, value length).
     ``fragments``: a list that receives the fragments of an encapsulated (7FE0,0010) -- RLE Lossless, JPEG Lossless with
-    ``frame_table`` (``_fragments``); None refuses them."""
+    ``frame_table`` (``_fragments``); None refuses them; ``_HEADER_ONLY`` returns at the value's first item."""
     e = ">" if big else "<"
     g, el = struct.unpack_from(e + "HH", buf, pos)
     pos += 4
@@ -201,6 +221,8 @@ def _element(buf: memoryview, pos: int, explicit: bool, big: bool, fragments: li
     start = pos
     if ln == 0xFFFFFFFF:
         if (g, el) == (0x7FE0, 0x0010):
+            if fragments is _HEADER_ONLY:
+                return pos, (g, el), vr, start, -1
             if fragments is not None:
                 return _fragments(buf, pos, fragments, frame_table), (g, el), vr, start, -1
             raise NotImplementedError("encapsulated (compressed) Pixel Data: decoded by pydicom's codec plug-ins, not by this path")
@@ -230,22 +252,24 @@ class _PrefixTooShort(Exception):
     """the prefix of a member ends before its (7FE0,0010) element header"""
 
 
-def _walk_part10(buf: memoryview, size: int | None = None, jpeg_lossless: bool = False) -> Metadata:
+def _walk_part10(buf: memoryview, size: int | None = None, jpeg_lossless: bool = False, encapsulated: bool = False) -> Metadata:
     """The element walk of ``read_part10`` over ``buf``.  ``size`` None: ``buf`` is the whole file.  Otherwise the PREFIX form
     ``load_zip`` uses: ``buf`` holds the first bytes of a file of ``size`` bytes, the walk stops at the Pixel Data element
     header -- (offset, length) of its value are validated against ``size``, not against the prefix -- and raises
-    ``_PrefixTooShort`` when the prefix ends before it (an element that is cut off is never read)."""
+    ``_PrefixTooShort`` when the prefix ends before it (an element that is cut off is never read).  ``encapsulated`` (the
+    prefix form only): a Pixel Data element of undefined length in an RLE Lossless or a JPEG Lossless file ends the walk too,
+    ``PixelData`` = (offset of its first item, -1); the items are walked on the device."""
     n = len(buf)
     whole = size is None or n >= size
     try:
-        return _walk_elements(buf, n, size, whole, jpeg_lossless)
+        return _walk_elements(buf, n, size, whole, jpeg_lossless, encapsulated and size is not None)
     except struct.error:
         if whole:
             raise
         raise _PrefixTooShort from None
 
 
-def _walk_elements(buf: memoryview, n: int, size, whole: bool, jpeg_lossless: bool = False) -> Metadata:
+def _walk_elements(buf: memoryview, n: int, size, whole: bool, jpeg_lossless: bool = False, items_later: bool = False) -> Metadata:
     pos = 132 if n >= 132 and bytes(buf[128:132]) == b"DICM" else 0
     values: dict = {}
     ts = IMPLICIT_LE if pos == 0 else EXPLICIT_LE          # (no preamble, force=True: pydicom assumes implicit VR little endian)
@@ -263,16 +287,20 @@ def _walk_elements(buf: memoryview, n: int, size, whole: bool, jpeg_lossless: bo
         explicit, big = True, False                         # every encapsulated syntax is explicit VR little endian
     else:
         explicit, big = ts != IMPLICIT_LE, ts == EXPLICIT_BE
-    if size is not None and ts == RLE_LOSSLESS:
+    if size is not None and ts == RLE_LOSSLESS and not items_later:
         raise NotImplementedError("RLE Lossless Pixel Data inside an archive: the segment headers lie inside the compressed part; "
                                   "extract the member and use load_frames")
     jpegll = jpeg_lossless and size is None and ts in JPEG_LOSSLESS
     fragments = [] if ts == RLE_LOSSLESS or jpegll else None
+    if items_later and (ts == RLE_LOSSLESS or ts in JPEG_LOSSLESS):
+        fragments = _HEADER_ONLY
     frame_table = [] if jpegll else None
     while pos + 8 <= n:
         pos, tag, vr, start, ln = _element(buf, pos, explicit, big, fragments, frame_table)
         if size is not None and tag == (0x7FE0, 0x0010):    # the prefix form ends here: the value is judged against the file
-            if start > size or ln > size - start:
+            if ln < 0 and start > size:
+                raise ValueError(f"the encapsulated Pixel Data value (at offset {start}) lies outside the file ({size} bytes)")
+            if ln >= 0 and (start > size or ln > size - start):
                 raise ValueError(f"the Pixel Data value ({ln} bytes at offset {start}) lies outside the file ({size} bytes)")
             values["PixelData"] = (start, ln)
             break
@@ -391,6 +419,14 @@ def decode_rle_frames(file_bytes, seg_off, seg_len, rows: int, cols: int, bits_a
     check(lib.pl_dicom_rle_decode(buf.data_ptr(), buf.numel(), so.data_ptr(), sl.data_ptr(), n, segments, int(max_segment_bytes),
                                   rows, cols, native.data_ptr(), status.data_ptr(), work.data_ptr(),
                                   torch.cuda.current_stream(dev).cuda_stream), "pl_dicom_rle_decode")
+    return _from_native(native, status[:n], cont, rows, cols, bits, bits_stored, rep, correct_unused_bits, out, rescale, dev)
+
+
+def _from_native(native: torch.Tensor, status: torch.Tensor, cont, rows: int, cols: int, bits: int, bits_stored, rep: int,
+                 correct_unused_bits: bool, out: str, rescale, dev) -> torch.Tensor:
+    """The tail the RLE and the JPEG Lossless decodes share: the decoded little-endian buffer [N, frame bytes] -> [N, rows,
+    cols] -- a view for the plain container dtype, through ``pl_dicom_decode`` otherwise -- carrying ``status``."""
+    n, frame_bytes = int(native.shape[0]), int(native.shape[1])
     stored = bits if bits_stored is None else int(bits_stored)
     if out == "container" and not (correct_unused_bits and stored < bits):
         res = native.view(cont).reshape(n, rows, cols)
@@ -398,17 +434,19 @@ def decode_rle_frames(file_bytes, seg_off, seg_len, rows: int, cols: int, bits_a
         res = decode_frames(native.reshape(-1), torch.arange(n, dtype=torch.int64, device=dev) * frame_bytes, rows, cols, bits,
                             stored, rep, big_endian=False, correct_unused_bits=correct_unused_bits, out=out, rescale=rescale,
                             device=dev)
-    res._pl_status = status[:n]
+    res._pl_status = status
     return res
 
 
-def _rle_segments(buf: np.ndarray, fragment: tuple, segments: int, name: str):
+def _rle_segments(header, fragment: tuple, segments: int, name: str):
     """The 64-byte header of one RLE fragment (PS3.5 section G.5: the number of segments, then 15 offsets from the start of the
-    header) -> [(offset inside ``buf``, length)] of its segments; ``ValueError`` for a header that is malformed."""
+    header) -> [(offset, length)] of its segments, in the frame of reference of ``fragment`` = (offset, length); ``header``:
+    the fragment's first bytes (64 of them are read when the fragment is that long).  ``ValueError`` for a header that is
+    malformed."""
     off, ln = fragment
     if ln < 64:
         raise ValueError(f"{name}: the RLE fragment is shorter than its 64-byte header")
-    head = struct.unpack_from("<16I", buf, off)
+    head = struct.unpack_from("<16I", header, 0)
     if head[0] != segments:
         raise ValueError(f"{name}: the RLE header states {head[0]} segments where BitsAllocated / 8 = {segments} are expected")
     offs = list(head[1:1 + segments])
@@ -433,6 +471,18 @@ def _check_rle_status(status: torch.Tensor, owner, names) -> None:
 def _jpegll_cols(cols: int) -> None:
     if cols > JPEGLL_MAX_COLS:
         raise ValueError(f"JPEG Lossless frames of {cols} columns: the device decode buffers rows of at most {JPEGLL_MAX_COLS} samples")
+
+
+def _jpegll_refusals(ib: int, cols: int) -> None:
+    """what a JPEG Lossless stack is refused for before any of its streams is read (``load_frames`` and ``load_zip``)"""
+    if ib not in (1, 2):
+        raise NotImplementedError(f"JPEG Lossless Pixel Data with BitsAllocated {ib * 8}: 8 and 16 are decoded on the device")
+    _jpegll_cols(cols)
+
+
+def _rle_fragment_count(found: list, frames: int, name: str) -> None:
+    if len(found) != frames:
+        raise ValueError(f"{name}: {len(found)} RLE fragments for NumberOfFrames = {frames} (one fragment per frame)")
 
 
 def decode_jpeg_lossless_frames(file_bytes, scan_off, scan_len, params, huff, rows: int, cols: int, bits_allocated: int,
@@ -476,15 +526,7 @@ def decode_jpeg_lossless_frames(file_bytes, scan_off, scan_len, params, huff, ro
     check(lib.pl_dicom_jpegll_decode(buf.data_ptr(), buf.numel(), so.data_ptr(), sl.data_ptr(), par.data_ptr(), tab.data_ptr(), n,
                                      rows, cols, bits // 8, native.data_ptr(), status.data_ptr(), work.data_ptr(),
                                      torch.cuda.current_stream(dev).cuda_stream), "pl_dicom_jpegll_decode")
-    stored = bits if bits_stored is None else int(bits_stored)
-    if out == "container" and not (correct_unused_bits and stored < bits):
-        res = native.view(cont).reshape(n, rows, cols)
-    else:
-        res = decode_frames(native.reshape(-1), torch.arange(n, dtype=torch.int64, device=dev) * frame_bytes, rows, cols, bits,
-                            stored, rep, big_endian=False, correct_unused_bits=correct_unused_bits, out=out, rescale=rescale,
-                            device=dev)
-    res._pl_status = status[:n]
-    return res
+    return _from_native(native, status[:n], cont, rows, cols, bits, bits_stored, rep, correct_unused_bits, out, rescale, dev)
 
 
 _SOF_REFUSED = {0xC0: "SOF0 (baseline DCT)", 0xC1: "SOF1 (extended sequential DCT)", 0xC2: "SOF2 (progressive DCT)",
@@ -496,14 +538,25 @@ _SOF_REFUSED = {0xC0: "SOF0 (baseline DCT)", 0xC1: "SOF1 (extended sequential DC
                 0xDF: "EXP (hierarchical)"}
 
 
-def _jpegll_header(data, rows: int, cols: int, bits: int, name: str):
+def _jpegll_header(data, rows: int, cols: int, bits: int, name: str, total: int | None = None):
     """The markers of one frame's JPEG stream up to its scan (T.81 Annex B) -> (offset of the entropy-coded segment inside
-    ``data``, its length up to the end of ``data``, [P, selection value, Pt, restart interval], the 33 bytes BITS + HUFFVAL
-    of the table SOS selects).  Every offset is checked against ``data``.  ``NotImplementedError`` for a process other than
+    ``data``, its length up to the end of the stream, [P, selection value, Pt, restart interval], the 33 bytes BITS + HUFFVAL
+    of the table SOS selects).  Every offset is checked against the stream.  ``NotImplementedError`` for a process other than
     Huffman-coded lossless (any SOFn but SOF3, DAC, DNL, hierarchical markers) and for more than one component;
-    ``ValueError`` for a malformed stream."""
+    ``ValueError`` for a malformed stream.  ``total``: ``data`` holds only the first bytes of a stream of ``total`` bytes
+    (``load_zip``: the stream lies on the device); a check that fails only because ``data`` ends raises ``_PrefixTooShort``,
+    a malformed stream is reported when it is certain."""
     data = bytes(data)
     n = len(data)
+    size = n if total is None else total                    # the stream's length
+
+    def ends(text):                                         # the bytes given end here: the stream's end, or only the prefix's
+        if n < size:
+            raise _PrefixTooShort
+        raise ValueError(f"{name}: {text}")
+
+    if n < 2 and n < size:
+        raise _PrefixTooShort
     if n < 2 or data[:2] != b"\xff\xd8":
         raise ValueError(f"{name}: the JPEG stream does not start with SOI")
     pos, tables, interval, frame = 2, {}, 0, None
@@ -511,7 +564,7 @@ def _jpegll_header(data, rows: int, cols: int, bits: int, name: str):
         while pos + 1 < n and data[pos] == 0xFF and data[pos + 1] == 0xFF:         # fill bytes before a marker (B.1.1.2)
             pos += 1
         if pos + 2 > n:
-            raise ValueError(f"{name}: the JPEG stream ends without SOS (no scan)")
+            ends("the JPEG stream ends without SOS (no scan)")
         if data[pos] != 0xFF:
             raise ValueError(f"{name}: a JPEG marker was expected at byte {pos} of the frame")
         m = data[pos + 1]
@@ -521,10 +574,12 @@ def _jpegll_header(data, rows: int, cols: int, bits: int, name: str):
             pos += 2
             continue
         if pos + 4 > n:
-            raise ValueError(f"{name}: the JPEG stream ends without SOS (no scan)")
+            ends("the JPEG stream ends without SOS (no scan)")
         ln = struct.unpack_from(">H", data, pos + 2)[0]
-        if ln < 2 or pos + 2 + ln > n:
+        if ln < 2 or pos + 2 + ln > size:
             raise ValueError(f"{name}: the segment of marker FF{m:02X} lies outside the fragment")
+        if pos + 2 + ln > n:
+            raise _PrefixTooShort
         seg = data[pos + 4:pos + 2 + ln]
         if m in _SOF_REFUSED:
             raise NotImplementedError(f"{name}: {_SOF_REFUSED[m]}, marker FF{m:02X}: only Huffman-coded lossless JPEG (SOF3) "
@@ -551,20 +606,20 @@ def _jpegll_header(data, rows: int, cols: int, bits: int, name: str):
                     raise ValueError(f"{name}: a DHT table definition is cut off")
                 tc, th = seg[at] >> 4, seg[at] & 15
                 counts = seg[at + 1:at + 17]
-                total = sum(counts)
+                symbols = sum(counts)
                 if tc != 0 or th > 3:
                     raise ValueError(f"{name}: DHT table class {tc}, id {th}: lossless scans use class 0, ids 0 .. 3")
-                if total > 17:
-                    raise ValueError(f"{name}: a DHT table of {total} symbols (at most 17 categories, 0 .. 16)")
-                if at + 17 + total > len(seg):
+                if symbols > 17:
+                    raise ValueError(f"{name}: a DHT table of {symbols} symbols (at most 17 categories, 0 .. 16)")
+                if at + 17 + symbols > len(seg):
                     raise ValueError(f"{name}: a DHT table definition is cut off")
-                values = seg[at + 17:at + 17 + total]
+                values = seg[at + 17:at + 17 + symbols]
                 if any(v > 16 for v in values):
                     raise ValueError(f"{name}: a DHT table holds the symbol {max(values)} (categories 0 .. 16)")
                 if sum(c << (15 - k) for k, c in enumerate(counts)) > 1 << 16:
                     raise ValueError(f"{name}: a DHT table is over-subscribed (Kraft sum above 1)")
-                tables[th] = bytes(counts) + values + b"\xff" * (17 - total)     # (a later definition replaces the earlier)
-                at += 17 + total
+                tables[th] = bytes(counts) + values + b"\xff" * (17 - symbols)   # (a later definition replaces the earlier)
+                at += 17 + symbols
         elif m == 0xDD:
             if ln != 4:
                 raise ValueError(f"{name}: malformed DRI segment")
@@ -587,7 +642,7 @@ def _jpegll_header(data, rows: int, cols: int, bits: int, name: str):
                 raise ValueError(f"{name}: the restart interval {interval} is not a whole number of rows of {cols} samples "
                                  "(T.81 H.1.1)")
             start = pos + 2 + ln
-            return start, n - start, [frame[0], ss, al, interval], tables[td]
+            return start, size - start, [frame[0], ss, al, interval], tables[td]
         pos += 2 + ln                                                               # APPn, COM, DQT, ...: skipped
 
 
@@ -633,6 +688,10 @@ def _check_status(frames: torch.Tensor) -> torch.Tensor:
     return frames
 
 
+_MIXED_JPEGLL = "load_frames: JPEG Lossless files are mixed with native or RLE Lossless files; load the kinds separately"
+_MIXED_RLE = "load_frames: native and RLE Lossless files are mixed; load the two kinds separately"
+
+
 def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bool | None = None,
                 correct_unused_bits: bool = False, device=None, check: bool = True, jpeg_lossless: bool = False):
     """The batched loader: Part-10 files (paths, bytes or file objects; every file may hold several frames) of ONE pixel
@@ -662,11 +721,11 @@ def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bo
     kinds = {"jpegll" if "PixelDataOffsetTable" in m else "rle" if "PixelDataFragments" in m else "native" for m in metas}
     if "jpegll" in kinds:
         if len(kinds) > 1:
-            raise ValueError("load_frames: JPEG Lossless files are mixed with native or RLE Lossless files; load the kinds separately")
+            raise ValueError(_MIXED_JPEGLL)
         return _load_jpegll(metas, blobs, lay, names, dtype, raw_pixels, invert_pixels, correct_unused_bits, device, check), metas
     rle = ["PixelDataFragments" in m for m in metas]
     if any(rle) and not all(rle):
-        raise ValueError("load_frames: native and RLE Lossless files are mixed; load the two kinds separately")
+        raise ValueError(_MIXED_RLE)
     rle = all(rle) and bool(metas)
     # one host buffer, every file at a 4-byte boundary; frame offsets (RLE: segment windows) inside it
     starts, offsets, owner, pos = [], [], [], 0
@@ -676,10 +735,9 @@ def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bo
         frames = l[3]
         if rle:
             found = metas[k].PixelDataFragments
-            if len(found) != frames:
-                raise ValueError(f"{names[k]}: {len(found)} RLE fragments for NumberOfFrames = {frames} (one fragment per frame)")
+            _rle_fragment_count(found, frames, names[k])
             for frag in found:
-                offsets.append([(pos + o, n) for o, n in _rle_segments(b, frag, ib, names[k])])
+                offsets.append([(pos + o, n) for o, n in _rle_segments(b[frag[0]:frag[0] + 64], frag, ib, names[k])])
                 owner.append(k)
             pos += (len(b) + 3) & ~3
             continue
@@ -747,9 +805,7 @@ def _jpegll_stage(metas, blobs, lay, names):
     """The host side of a JPEG Lossless stack -> (the staging buffer, (scan_off, scan_len, params, huff) as
     ``decode_jpeg_lossless_frames`` takes them, the file of every frame); every refusal of a file happens here."""
     _, _, ib, _, rows, cols, _, _ = lay[0]
-    if ib not in (1, 2):
-        raise NotImplementedError(f"JPEG Lossless Pixel Data with BitsAllocated {ib * 8}: 8 and 16 are decoded on the device")
-    _jpegll_cols(cols)
+    _jpegll_refusals(ib, cols)
     pieces, owner, scan_off, scan_len, params, huff, pos = [], [], [], [], [], [], 0
     for k, (m, b, l) in enumerate(zip(metas, blobs, lay)):
         for frags in _jpegll_frames(m, l[3], names[k]):
@@ -826,18 +882,21 @@ def _finish_frames(decode, verify, metas, owner, rows: int, cols: int, dtype, ra
     return x
 
 
-def _member_header(raw, member, what: str):
+def _member_header(raw, member, what: str, encapsulated: bool = False):
     """The Part-10 header of one archive member without inflating it whole -> its metadata, or None for a member without
     ``DICM`` at byte 128.  ``raw``: the member's bytes as they lie in the archive (a uint8 array view).  A stored member is
     walked where it lies; of a deflated one the first 64 KiB are inflated on the host, and twice as many again until the walk
-    reaches the (7FE0,0010) element header or the member ends."""
+    reaches the (7FE0,0010) element header or the member ends.  ``encapsulated``: ``_walk_part10``'s."""
     import zlib
+
+    def walk(view, size):                                   # (the default path calls _walk_part10 as it always did)
+        return _walk_part10(view, size, encapsulated=True) if encapsulated else _walk_part10(view, size)
 
     if member.size < 132:
         return None
     if member.method == 0:
         view = memoryview(raw).cast("B")
-        return _walk_part10(view, member.size) if bytes(view[128:132]) == b"DICM" else None
+        return walk(view, member.size) if bytes(view[128:132]) == b"DICM" else None
     inflater, have, want, data = zlib.decompressobj(-15), bytearray(), 65536, memoryview(raw).cast("B")
     while True:
         try:
@@ -849,7 +908,7 @@ def _member_header(raw, member, what: str):
             return None
         ended = inflater.eof or (len(have) < want and not data)
         try:
-            return _walk_part10(memoryview(have), len(have) if ended else max(member.size, len(have) + 1))
+            return walk(memoryview(have), len(have) if ended else max(member.size, len(have) + 1))
         except _PrefixTooShort:
             if ended:
                 raise zipfile.BadZipFile(f"{what}: the Deflate stream ends inside the data set's header") from None
@@ -857,17 +916,28 @@ def _member_header(raw, member, what: str):
 
 
 def load_zip(source, members=None, verify: bool = True, dtype=None, raw_pixels: bool = False, invert_pixels: bool | None = None,
-             correct_unused_bits: bool = False, device=None, check: bool = True):
+             correct_unused_bits: bool = False, device=None, check: bool = True, encapsulated: bool = False):
     """``load_frames([zf.read(n) for n in names], ...)`` for a ZIP archive of native Part-10 files (what
     ``DicomImageStack.from_zip`` / ``CatPhan504.from_zip`` are handed) without a member ever being inflated whole on the host
     -> (device tensor [N, H, W], list of per-member metadata, names).  The archive goes to the device compressed; ONE
     ``pl_zip_extract`` (``zipstack.extract``) inflates every member with a wave of its own and, with ``verify``, checks its
     CRC-32 as ``zipfile`` does; ``pl_dicom_decode`` then reads the frames where the members lie.  The host inflates only each
     member's first kilobytes, for the Part-10 header walk.  ``members``: names in the order wanted; None takes every member
-    with ``DICM`` at byte 128, in central-directory order (``names`` lists them).  RLE Lossless members raise
-    ``NotImplementedError`` naming the member (their segment headers lie inside the compressed part); the other refusals, the
+    with ``DICM`` at byte 128, in central-directory order (``names`` lists them).  By default RLE Lossless members raise
+    ``NotImplementedError`` naming the member (``encapsulated=True``, below, decodes them); the other refusals, the
     dtype rules, rescale and inversion are ``load_frames``'s own.  ``check=True`` reads the archive's status once
     (``zipfile.BadZipFile``: ``Bad CRC-32 for file 'NAME'``) and the decode's.
+
+    ``encapsulated=True`` extends the same contract to the members a CT series usually leaves a PACS with:
+    ``load_frames([zf.read(n) for n in names], jpeg_lossless=True, ...)`` for archives whose members are all RLE Lossless or
+    all JPEG Lossless (``JPEG_LOSSLESS``) -- the same tensor, metadata (``PixelData`` = (offset, -1), ``PixelDataFragments``,
+    ``PixelDataOffsetTable``), kind-mixing rules and refusals, the member named ``ARCHIVE: member 'NAME'``.  The host's header
+    walk stops at the Pixel Data element; after the extraction ONE ``pl_dicom_encap_index`` (``index_encapsulated``) walks
+    every member's items on the device and ONE transfer brings back, per fragment, its place and its first
+    ``ENCAP_HEAD_BYTES`` bytes, from which the host reads RLE segment headers and JPEG markers.  The fragments are decoded
+    where the members lie; only a JPEG frame that spans fragments is first laid end to end (``copy_ranges``), and only a frame
+    whose markers run past the head has its leading bytes fetched (4 KiB, doubling).  No Pixel Data comes back to the host.
+    Without the keyword such members raise ``NotImplementedError`` as they always did.
 
     The device form is for archives of MANY members of moderate size -- a CT volume: 80 - 300 slices of 0.5 MB, every Deflate
     stream a wave of its own.  One Deflate stream is one serial chain (about 150 ns per output byte), so an archive of a few
@@ -881,7 +951,7 @@ def load_zip(source, members=None, verify: bool = True, dtype=None, raw_pixels: 
     for m in zipstack._select(archive, members, what):
         name = f"{what}: member {m.name!r}"
         try:
-            meta = _member_header(hv[m.data_offset:m.data_offset + m.compressed_size], m, name)
+            meta = _member_header(hv[m.data_offset:m.data_offset + m.compressed_size], m, name, encapsulated)
         except NotImplementedError as e:
             raise NotImplementedError(f"{name}: {e}") from None
         if meta is None:
@@ -898,6 +968,13 @@ def load_zip(source, members=None, verify: bool = True, dtype=None, raw_pixels: 
     for l in lay[1:]:
         if (l[0], l[4], l[5], l[6]) != (tdt, rows, cols, big):
             raise ValueError("load_zip: the members differ in pixel format or frame size (the reference's stacks refuse that too)")
+    kinds = {"native" if m.PixelData[1] >= 0 else "rle" if m.TransferSyntaxUID == RLE_LOSSLESS else "jpegll" for m in metas}
+    if len(kinds) > 1:                                      # (load_frames's rule, in its words)
+        raise ValueError(_MIXED_JPEGLL if "jpegll" in kinds else _MIXED_RLE)
+    if kinds != {"native"}:
+        x = _load_zip_encapsulated(kinds.pop(), taken, metas, lay, what, host, dbuf, verify, check, dtype, raw_pixels,
+                                   invert_pixels, correct_unused_bits)
+        return x, metas, names
     inside, owner = [], []                                  # frame offsets inside each member
     for k, (m, l) in enumerate(zip(taken, lay)):
         off, ln = l[7]
@@ -920,6 +997,275 @@ def load_zip(source, members=None, verify: bool = True, dtype=None, raw_pixels: 
 
     x = _finish_frames(decode, _check_status, metas, owner, rows, cols, dtype, raw_pixels, invert_pixels, check)
     return x, metas, names
+
+
+ENCAP_HEAD_BYTES = 256                                       # PL_DICOM_ENCAP_HEAD: the bytes of every fragment the index brings back
+ENCAP_DESCRIPTOR, ENCAP_MALFORMED, ENCAP_TABLE, ENCAP_CAPACITY, ENCAP_NO_DELIMITER, ENCAP_TABLE_LENGTH = 1, 2, 4, 8, 16, 32
+
+
+@dataclass
+class EncapIndex:
+    """What ``index_encapsulated`` returns: ``block``, the result block of ``pl_dicom_encap_index`` (uint8, on the device),
+    and views of its parts -- ``frags`` int64 [M, cap, 3] (payload offset, length, offset of the item tag, all inside the
+    buffer), ``heads`` uint8 [M, cap, head_bytes], ``info`` int32 [M, 4] (status, fragments found, table entries found, 0),
+    ``table`` uint32 [M, tcap].  ``host()``: the same views as numpy arrays after ONE transfer of the block."""
+    block: torch.Tensor
+    members: int
+    cap: int
+    tcap: int
+    head_bytes: int
+
+    def _parts(self):
+        m, cap, tcap, h = self.members, self.cap, self.tcap, self.head_bytes
+        heads = m * cap * 24
+        info = heads + m * cap * h
+        table = info + m * 16
+        return ((0, heads, "int64", (m, cap, 3)), (heads, info, "uint8", (m, cap, h)), (info, table, "int32", (m, 4)),
+                (table, table + m * tcap * 4, "uint32", (m, tcap)))
+
+    def views(self):
+        """-> (frags, heads, info, table): views of the block where it lies"""
+        return [self.block[a:b].view(getattr(torch, dt)).reshape(shape) for a, b, dt, shape in self._parts()]
+
+    frags = property(lambda self: self.views()[0])
+    heads = property(lambda self: self.views()[1])
+    info = property(lambda self: self.views()[2])
+    table = property(lambda self: self.views()[3])
+
+    def host(self):
+        """-> (frags, heads, info, table) as numpy arrays: one transfer"""
+        block = self.block.cpu().numpy()
+        return [block[a:b].view(dt).reshape(shape) for a, b, dt, shape in self._parts()]
+
+
+def index_encapsulated(buffer, first, end, cap: int, tcap: int, head_bytes: int = ENCAP_HEAD_BYTES, device=None,
+                       block: torch.Tensor | None = None) -> EncapIndex:
+    """``pl_dicom_encap_index``: the items of M encapsulated Pixel Data values lying anywhere inside ``buffer`` (uint8 array /
+    tensor; a device tensor is used in place), one wave per value, nothing read back -> ``EncapIndex``.  Value m: its first
+    item (the Basic Offset Table's) starts at byte ``first[m]``, and nothing at or beyond byte ``end[m]`` belongs to it.  Up
+    to ``cap`` fragments and ``tcap`` table entries per value are stored, all are counted.  Status bits (``info[:, 0]``):
+    ``ENCAP_DESCRIPTOR`` the window lies outside the buffer (nothing but the status is stored), ``ENCAP_MALFORMED`` an item
+    that is none (with ``ENCAP_NO_DELIMITER``: the value ends without its delimiter), ``ENCAP_TABLE`` no table item (with
+    ``ENCAP_TABLE_LENGTH``: its length is no multiple of 4), ``ENCAP_CAPACITY`` more fragments than ``cap`` or entries than
+    ``tcap``.  ``block``: a uint8 device tensor of the block's size to write into."""
+    dev = on_device(device)
+    buf = bytes_tensor(buffer, dev)
+    nbytes = int(buf.numel())
+    if nbytes == 0:
+        buf = torch.zeros(4, dtype=torch.uint8, device=dev)
+    lo, hi = index_tensor(first, torch.int64, dev).reshape(-1), index_tensor(end, torch.int64, dev).reshape(-1)
+    m = int(lo.numel())
+    if int(hi.numel()) != m:
+        raise ValueError("index_encapsulated: first / end [M]")
+    lib = _lib.load()
+    need = int(lib.pl_dicom_encap_index_bytes(m, int(cap), int(tcap), int(head_bytes)))
+    if need < 0:
+        raise ValueError(f"index_encapsulated: M = {m}, cap = {cap}, tcap = {tcap}, head_bytes = {head_bytes} are out of range")
+    if block is None:
+        block = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif block.dtype != torch.uint8 or block.dim() != 1 or int(block.numel()) != need or not block.is_contiguous() or not block.is_cuda:
+        raise ValueError(f"index_encapsulated: block must be a contiguous uint8 device tensor of {need} bytes")
+    check(lib.pl_dicom_encap_index(buf.data_ptr(), nbytes, lo.data_ptr(), hi.data_ptr(), m, int(cap), int(tcap), int(head_bytes),
+                                   block.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "pl_dicom_encap_index")
+    return EncapIndex(block, m, int(cap), int(tcap), int(head_bytes))
+
+
+def copy_ranges(src, dst: torch.Tensor, src_off, length, dst_off, device=None) -> torch.Tensor:
+    """``pl_copy_ranges``: R byte ranges of ``src`` (uint8 array / tensor; a device tensor is used in place) into ``dst`` (a
+    contiguous uint8 device tensor), any alignment on either side: range r is the ``length[r]`` bytes at ``src_off[r]``, they
+    go to ``dst_off[r]``; no other byte of ``dst`` is written.  -> status int32 [R] on the device: 1 for a range that does not
+    lie inside both buffers (nothing of it is copied).  An upper bound of the lengths is taken from a host array; a device
+    tensor is reduced and read back once."""
+    dev = on_device(device)
+    buf = bytes_tensor(src, dev)
+    if dst.dtype != torch.uint8 or dst.dim() != 1 or not dst.is_contiguous() or not dst.is_cuda:
+        raise ValueError("copy_ranges: dst must be a contiguous uint8 device tensor")
+    so, ln, do = (index_tensor(a, torch.int64, dev).reshape(-1) for a in (src_off, length, dst_off))
+    r = int(so.numel())
+    if int(ln.numel()) != r or int(do.numel()) != r:
+        raise ValueError("copy_ranges: src_off / length / dst_off [R]")
+    status = torch.empty(max(r, 1), dtype=torch.int32, device=dev)
+    if r == 0:
+        return status[:0]
+    longest = int(length.max()) if isinstance(length, torch.Tensor) else int(np.max(length, initial=0))
+    src_bytes, dst_bytes = int(buf.numel()), int(dst.numel())
+    if src_bytes == 0:
+        buf = torch.zeros(4, dtype=torch.uint8, device=dev)
+    if dst_bytes == 0:
+        dst = torch.zeros(4, dtype=torch.uint8, device=dev)
+    check(_lib.load().pl_copy_ranges(buf.data_ptr(), src_bytes, dst.data_ptr(), dst_bytes, so.data_ptr(), ln.data_ptr(),
+                                     do.data_ptr(), r, max(longest, 0), status.data_ptr(),
+                                     torch.cuda.current_stream(dev).cuda_stream), "pl_copy_ranges")
+    return status
+
+
+def _index_members(stack, metas, lay, names, frames_span: bool) -> list:
+    """The item walk of every member's Pixel Data on the device (``index_encapsulated``, a second call with the exact counts
+    when the first guess of the capacities overflows) and ``_fragments``' checks on what ONE transfer brings back: the
+    members' metadata receive ``PixelDataFragments`` (and ``PixelDataOffsetTable`` with ``frames_span``, JPEG Lossless) as
+    ``read_part10`` states them -> the heads of every member's fragments, uint8 [fragments, ENCAP_HEAD_BYTES] each."""
+    base, dev = stack.offsets, stack.buffer.device
+    first = base + np.asarray([m.PixelData[0] for m in metas], dtype=np.int64)
+    most = max(l[3] for l in lay)
+    cap, tcap = max(16, 2 * most), max(most, 1)
+    while True:
+        frags, heads, info, table = index_encapsulated(stack.buffer, first, base + stack.sizes, cap, tcap, device=dev).host()
+        if not (info[:, 0] & ENCAP_CAPACITY).any():
+            break
+        walked = info[(info[:, 0] & ENCAP_DESCRIPTOR) == 0]                         # (an unsound descriptor leaves no counts)
+        cap, tcap = max(int(walked[:, 1].max()), 1), max(int(walked[:, 2].max()), 1)  # the exact counts: it cannot overflow again
+    out = []
+    for k, (meta, name) in enumerate(zip(metas, names)):
+        status, n_frag, n_table = (int(v) for v in info[k, :3])
+        for bit, text in ((ENCAP_DESCRIPTOR, "the encapsulated Pixel Data value lies outside the member"),
+                          (ENCAP_NO_DELIMITER, _ITEMS_NO_DELIMITER), (ENCAP_MALFORMED, _ITEMS_NO_ITEM),
+                          (ENCAP_TABLE_LENGTH, _ITEMS_TABLE_LENGTH), (ENCAP_TABLE, _ITEMS_NO_TABLE)):
+            if status & bit:
+                raise ValueError(f"{name}: {text}")
+        inside = frags[k, :n_frag] - np.asarray([base[k], 0, base[k]], dtype=np.int64)
+        entries = [int(v) for v in table[k, :n_table]]
+        try:
+            _check_offset_table(entries, [int(t) for t in inside[:, 2]], frames_span)
+        except ValueError as e:
+            raise ValueError(f"{name}: {e}") from None
+        meta._values["PixelDataFragments"] = [(int(o), int(n)) for o, n, _ in inside]
+        if frames_span:
+            meta._values["PixelDataOffsetTable"] = entries
+        out.append(heads[k, :n_frag])
+    return out
+
+
+def _fetch_stream_head(buffer: torch.Tensor, pieces: list, nbytes: int) -> bytes:
+    """The first ``nbytes`` bytes of a stream whose pieces (offset, length) lie in a device buffer, laid end to end: plain
+    slice copies, one transfer (``load_zip``: a JPEG frame whose markers run past the head the index brought back)."""
+    parts = []
+    for off, ln in pieces:
+        take = min(ln, nbytes)
+        if take:
+            parts.append(buffer[off:off + take])
+        nbytes -= take
+        if nbytes <= 0:
+            break
+    return (parts[0] if len(parts) == 1 else torch.cat(parts)).cpu().numpy().tobytes() if parts else b""
+
+
+def _load_zip_encapsulated(kind: str, taken, metas, lay, what: str, host, dbuf, verify: bool, check: bool, dtype, raw_pixels: bool,
+                           invert_pixels, correct_unused_bits: bool):
+    """``load_zip(encapsulated=True)`` for members that are all RLE Lossless (``kind`` "rle") or all JPEG Lossless ("jpegll"):
+    the extraction, the item walk on the device, the host's reading of the heads, the decode where the members lie."""
+    from . import zipstack
+
+    names = [f"{what}: member {m.name!r}" for m in taken]
+    _, _, ib, _, rows, cols, _, _ = lay[0]
+    if kind == "jpegll":
+        _jpegll_refusals(ib, cols)
+    stack = zipstack.run(taken, what, host, dbuf, verify=verify, check=check)
+    dev, base = stack.buffer.device, stack.offsets
+    heads = _index_members(stack, metas, lay, names, kind == "jpegll")
+    stored = int(metas[0].get("BitsStored") or ib * 8)
+    common = dict(rows=rows, cols=cols, bits_allocated=ib * 8, bits_stored=stored,
+                  pixel_representation=int(metas[0].PixelRepresentation), correct_unused_bits=correct_unused_bits, device=dev)
+    owner, seen = [], []
+    if kind == "rle":
+        windows = []
+        for k, (meta, l) in enumerate(zip(metas, lay)):
+            found = meta.PixelDataFragments
+            _rle_fragment_count(found, l[3], names[k])
+            for j, frag in enumerate(found):
+                windows.append([(int(base[k]) + o, n) for o, n in _rle_segments(heads[k][j], frag, ib, names[k])])
+                owner.append(k)
+        windows = np.asarray(windows, dtype=np.int64).reshape(-1, ib, 2)
+        seg_off, seg_len = np.ascontiguousarray(windows[:, :, 0]), np.ascontiguousarray(windows[:, :, 1])
+
+        def decode(**kw):
+            x = decode_rle_frames(stack.buffer, seg_off, seg_len, max_segment_bytes=int(seg_len.max(initial=0)), **common, **kw)
+            seen.append(x._pl_status)
+            return x
+
+        def verify_frames(x):
+            _check_rle_status(seen[-1], owner, names)
+            return x
+    else:
+        decode, copied = _zip_jpegll_decode(stack, metas, lay, names, heads, owner, seen, common)
+
+        def verify_frames(x):
+            if copied is not None and bool(copied.any()):
+                raise ValueError(f"{what}: a fragment of a frame that spans fragments lies outside the extracted members")
+            _check_jpegll_status(seen[-1], owner, names)
+            return x
+    return _finish_frames(decode, verify_frames, metas, owner, rows, cols, dtype, raw_pixels, invert_pixels, check)
+
+
+def _zip_jpegll_decode(stack, metas, lay, names, heads, owner: list, seen: list, common: dict):
+    """The JPEG Lossless half of ``_load_zip_encapsulated``: every frame's markers parsed from the heads of its fragments
+    (``_jpegll_header``; leading bytes fetched from the device only when they run past the heads), a frame of one fragment
+    decoded where it lies, the frames that span fragments laid end to end at 4-byte boundaries of a staging buffer by ONE
+    ``copy_ranges`` -> (decode(out=, rescale=), the copy's status or None).  ``decode_jpeg_lossless_frames`` takes one
+    buffer: with both kinds of frames it is called once per buffer, into the two parts of one native tensor."""
+    _, _, ib, _, rows, cols, _, _ = lay[0]
+    dev, base = stack.buffer.device, stack.offsets
+    scan_off, scan_len, params, huff, staged, ranges, pos = [], [], [], [], [], [], 0
+    for k, (meta, l) in enumerate(zip(metas, lay)):
+        index_of = {o: j for j, (o, _) in enumerate(meta.PixelDataFragments)}
+        for frags in _jpegll_frames(meta, l[3], names[k]):
+            total = sum(n for _, n in frags)
+            pieces = [(int(base[k]) + o, n) for o, n in frags]
+            data = b""
+            for o, n in frags:                              # the heads, as far as they are the stream's leading bytes
+                data += heads[k][index_of[o]][:min(n, ENCAP_HEAD_BYTES)].tobytes()
+                if n > ENCAP_HEAD_BYTES:
+                    break
+            want = max(4096, 2 * len(data))                 # (the heads of many short fragments may hold more than 4 KiB)
+            while True:
+                try:
+                    start, length, par, table = _jpegll_header(data, rows, cols, ib * 8, names[k], total=total)
+                    break
+                except _PrefixTooShort:
+                    data = _fetch_stream_head(stack.buffer, pieces, min(want, total))
+                    want *= 2
+            if len(pieces) == 1:
+                scan_off.append(pieces[0][0] + start)
+            else:
+                at = pos
+                for o, n in pieces:
+                    ranges.append((o, n, at))
+                    at += n
+                scan_off.append(pos + start)
+                pos += (total + 3) & ~3
+            staged.append(len(pieces) > 1)
+            owner.append(k)
+            scan_len.append(length)
+            params.append(par)
+            huff.append(np.frombuffer(table, dtype=np.uint8))
+    scan_off, scan_len = np.asarray(scan_off, dtype=np.int64), np.asarray(scan_len, dtype=np.int64)
+    params, huff, staged = np.asarray(params, dtype=np.int32).reshape(-1, 4), np.stack(huff), np.asarray(staged, dtype=bool)
+    staging = copied = None
+    if ranges:
+        moves = np.asarray(ranges, dtype=np.int64)
+        staging = torch.empty(max(pos, 16), dtype=torch.uint8, device=dev)
+        copied = copy_ranges(stack.buffer, staging, moves[:, 0], moves[:, 1], moves[:, 2], device=dev)
+    groups = [(buf, np.flatnonzero(sel)) for buf, sel in ((stack.buffer, ~staged), (staging, staged)) if sel.any()]
+
+    def decode(**kw):
+        if len(groups) == 1:
+            x = decode_jpeg_lossless_frames(groups[0][0], scan_off, scan_len, params, huff, **common, **kw)
+        else:                                               # one call per buffer, then the frames back into their order
+            bits, rep = common["bits_allocated"], common["pixel_representation"]
+            native = torch.empty((scan_off.size, rows * cols * ib), dtype=torch.uint8, device=dev)
+            status, done = [], 0
+            for buf, idx in groups:
+                part = decode_jpeg_lossless_frames(buf, scan_off[idx], scan_len[idx], params[idx], huff[idx], rows, cols, bits,
+                                                   device=dev, native=native[done:done + idx.size])
+                status.append(part._pl_status)
+                done += idx.size
+            back = torch.from_numpy(np.argsort(np.concatenate([idx for _, idx in groups]))).to(dev)
+            cont = {(8, 0): torch.uint8, (8, 1): torch.int8, (16, 0): torch.uint16, (16, 1): torch.int16}[(bits, rep)]
+            x = _from_native(native[back], torch.cat(status)[back], cont, rows, cols, bits, common["bits_stored"], rep,
+                             common["correct_unused_bits"], kw.get("out", "container"), kw.get("rescale"), dev)
+        seen.append(x._pl_status)                            # (an integer astype hands on a tensor without it)
+        return x
+
+    return decode, copied
 
 
 def _astype(x: torch.Tensor, np_dt: np.dtype) -> torch.Tensor:

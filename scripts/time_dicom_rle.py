@@ -62,7 +62,7 @@ def main():
     for m, b in metas:
         starts.append(pos)
         (frag,) = m.PixelDataFragments
-        table.append([(pos + o, ln) for o, ln in dicom._rle_segments(b, frag, 2, "file")])
+        table.append([(pos + o, ln) for o, ln in dicom._rle_segments(b[frag[0]:frag[0] + 64], frag, 2, "file")])
         pos += (len(b) + 3) & ~3
     host = torch.zeros(pos, dtype=torch.uint8).pin_memory()
     for st, (_, b) in zip(starts, metas):
