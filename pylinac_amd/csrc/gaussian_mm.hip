@@ -25,7 +25,10 @@
 //   t_k = a_k + (t_{k-1} >> 8) = floor((2^8 a1 + .. + 2^(8k) a_k) / 2^(8k)),     bits 8k .. 8k+7 of T' = t_k & 255
 //   floor(S) = t_5 whenever T' mod 2^40 >= 2 M, i.e. whenever bits 24 .. 39 of T' are not all zero: z = (t3 | t4) & 255 != 0
 // The additions of the cascade are the MFMAs' own: level k's first MFMA takes (t_{k-1} >> 8) as its C operand (mm_tile).
-// Per output the VALU does four arithmetic right shifts, one add and the byte test -- full-rate opcodes only.
+// Per output the VALU does four arithmetic right shifts and the byte test -- full-rate opcodes only.  C' >> 40 is always
+// exactly 32896 (mm_make_params checks it): uint16 frames run the chain without it, level 5 is then floor(S) - 32896, and the
+// stores put it back two outputs at a time (one packed 16-bit add per register: mm_finish_flag); int16 frames add it where
+// level 4 starts.
 // z = 0 (1.5e-5 of the outputs, plus constant / saturated neighbourhoods where S sits 1e-11 from an integer) means
 // "undecided": recomputed with scipy's float64 sequence from the plane bytes still in LDS.
 //
@@ -37,7 +40,9 @@
 // Cost model (scripts/ubench/mfma_valu_settle.hip on the MI355X, profiles/r03a_ubench_mfma_valu_settle.txt): on one SIMD the
 // i8 MFMA (16 cycles, SQ_VALU_MFMA_BUSY_CYCLES = 16 x SQ_INSTS_MFMA) and the VALU (2.3 - 2.4 cycles per full-rate opcode from two
 // or more waves) do NOT overlap -- interleaved in one wave, blocked, or on partner waves, their times add.  A tile costs
-// 9 MFMA + ~37 VALU (50 with the plane split and addressing), which is what bounds this kernel (not HBM): DESIGN.md section 5.
+// 9 MFMA + ~30 VALU (41 with the plane split and the step's bookkeeping; before the constant left the chain, a pass made one
+// undecided test for all its tiles and inner row groups loaded through the scalar offset: ~37 and 50;
+// profiles/r25_gauss2d_block_counts.txt), which is what bounds this kernel (not HBM): DESIGN.md section 5.
 #include <type_traits>
 
 #include "pl_common.h"
@@ -52,14 +57,14 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 // Everything a pass needs, computed on the host (mm_make_params) and passed by value.
 constexpr int kMmDigits = 5;
 constexpr int kMmQ = 40;                      // taps are quantised to 2^-40
+constexpr long long kMmBias = 32896;          // 0x8080: what the two flipped top bits take off a sample, C' >> 40 (mm_make_params)
 
 struct MmParams {
   // band[d][c][.]: the zero-padded band sequence E_d[p] = digit_d[|p - 39|] (|p - 39| <= RAD, else 0) of weight digit d,
   // shifted left by c bytes, so that a lane whose Toeplitz row starts at p0 = 16 g - i + 15 reads its 16 bytes as four
   // ALIGNED dwords band[d][p0 & 3][(p0 >> 2) .. + 3]
   unsigned band[kMmDigits][4][24];
-  int c1;            // (C' mod 2^32) >> 8     -> initial value of level 1   (C' = 32896 * sum wq + M, M = 2^23)
-  int c4;            // C' >> 32               -> added where level 4 starts
+  int c1;            // (C' - 32896 * 2^40) >> 8 -> initial value of level 1  (C' = 32896 * sum wq + M, M = 2^23)
   int radius;
   double wd[kMmMaxRad + 1];  // float64 taps (offset j) for the exact path, zero beyond radius
 };
@@ -117,9 +122,13 @@ bool mm_make_params(const double* h_wts /* 2*R+1 taps, centre at R */, int R, Mm
   // floor(S) whatever the error within +-D <= M; "T' mod 2^Q < 2^24" is "bits 24 .. 39 of T' are all zero"
   constexpr long long M = 1LL << 23;
   if (!(D < (double)M)) return false;
-  const long long C = 32896LL * WQ + M;                                      // < 2^16 * 2^41
-  p.c1 = (int)((C & 0xffffffffLL) >> 8);
-  p.c4 = (int)(C >> 32);
+  // D < M needs |W - 1| < 2^-33, hence |WQ - 2^40| <= 2 R + 1 + 2^7 and C = 32896 * 2^40 + Clo with 0 < Clo < 2^24: the
+  // part above bit 40 is the CONSTANT 32896 = kMmBias, which the chain leaves out (level 5 then holds floor(S) - 32896); the
+  // rest rides on level 1.  Checked, not assumed: taps that miss it take the two-pass kernels like any uncovered taps
+  const long long C = 32896LL * WQ + M;
+  const long long Chi = C >> kMmQ, Clo = C - (Chi << kMmQ);
+  if (Chi != kMmBias || Clo >= (1LL << 32)) return false;
+  p.c1 = (int)(Clo >> 8);
   p.radius = R;
   for (int j = 0; j <= kMmMaxRad; ++j) p.wd[j] = j <= R ? h_wts[R - j] : 0.0;
   return true;
@@ -147,23 +156,31 @@ __device__ __forceinline__ double mm_exact(F raw /* k in [-R, R] -> actual value
   return a;
 }
 
-// One tile's result: v = floor(S) per output in the biased domain (0 .. 65535); z = bits 24 .. 39 of T' folded into a
-// byte: the output is decided iff z != 0.
+// One tile's result: v = floor(S) per output in the biased domain (0 .. 65535) -- LESS kMmBias when the chain ran without
+// it (FOLD: -32896 .. 32639); z = bits 24 .. 39 of T' folded into a byte: the output is decided iff z != 0.
 struct MmAcc { v4i v, z; };
 
-struct MmConst { v4i c1, c4; };                // level 1's initial value, level 4's added constant: one register quad each
+struct MmConst { v4i c1; };                    // level 1's initial value: one register quad
 __device__ __forceinline__ MmConst mm_const(const MmParams& P) {
-  return MmConst{v4i{P.c1, P.c1, P.c1, P.c1}, v4i{P.c4, P.c4, P.c4, P.c4}};
+  return MmConst{v4i{P.c1, P.c1, P.c1, P.c1}};
+}
+// FOLD = false: kMmBias joins where level 4 starts (scale 2^32: kMmBias * 256, low byte 0 -- the decision byte t4 & 255 is
+// the same either way) and level 5 is floor(S) itself
+template <bool FOLD>
+__device__ __forceinline__ v4i mm_level4(v4i t3) {
+  constexpr int kC4 = (int)(kMmBias * 256);
+  return FOLD ? t3 >> 8 : (t3 >> 8) + v4i{kC4, kC4, kC4, kC4};
 }
 
 // The nine MFMAs of one tile as a CARRY CHAIN: img_lo / img_hi = the 16 x 64 sample digit planes (as A when IMG_IS_A),
 // w[d] = Toeplitz band of weight digit d.  Level k (digit-pair scale 2^(8k)) starts from the level below shifted right by
 // eight -- the shifted value IS the MFMA's C operand, so the additions of the cascade
 //   t_k = a_k + (t_{k-1} >> 8) = floor((2^8 a1 + .. + 2^(8k) a_k) / 2^(8k)),     bits 8k .. 8k+7 of T' = t_k & 255
-// cost nothing: per output the VALU does four arithmetic shifts, one add (the part of the constant that does not fit
-// level 1's 32 bits) and the byte test.  floor(floor(x / a) / b) = floor(x / (a b)) keeps every level exact.  The low
-// sample digit x lowest weight digit product (scale 0) is below the decision's resolution: left out, its bound is in D.
-template <bool IMG_IS_A>
+// cost nothing: per output the VALU does four arithmetic shifts and the byte test (the part of the constant that does not
+// fit level 1's 32 bits is kMmBias: FOLD leaves it to whoever stores the result, mm_level4).  floor(floor(x / a) / b) =
+// floor(x / (a b)) keeps every level exact.  The low sample digit x lowest weight digit product (scale 0) is below the
+// decision's resolution: left out, its bound is in D.
+template <bool IMG_IS_A, bool FOLD>
 __device__ __forceinline__ MmAcc mm_tile(v4i img_lo, v4i img_hi, const v4i (&w)[kMmDigits], const MmConst& K) {
   auto mm = [&](v4i img, v4i band, v4i c) -> v4i {
     return IMG_IS_A ? __builtin_amdgcn_mfma_i32_16x16x64_i8(img, band, c, 0, 0, 0)
@@ -175,17 +192,17 @@ __device__ __forceinline__ MmAcc mm_tile(v4i img_lo, v4i img_hi, const v4i (&w)[
   t = mm(img_hi, w[1], t);
   v4i t3 = mm(img_lo, w[3], t >> 8);               // level 3
   t3 = mm(img_hi, w[2], t3);
-  v4i t4 = mm(img_lo, w[4], (t3 >> 8) + K.c4);     // level 4
+  v4i t4 = mm(img_lo, w[4], mm_level4<FOLD>(t3));  // level 4
   t4 = mm(img_hi, w[3], t4);
   MmAcc r;
-  r.v = mm(img_hi, w[4], t4 >> 8);                 // level 5 = floor(T' / 2^40)
+  r.v = mm(img_hi, w[4], t4 >> 8);                 // level 5 = floor(T' / 2^40) (FOLD: - kMmBias)
   r.z = (t3 | t4) & 255;
   return r;
 }
 
 // NT tiles in lock step, level by level: the MFMA of tile i at level k is followed by the other tiles' MFMAs of that level
 // before anything depends on it -- a single tile's chain would stall on the matrix pipe's latency after every level.
-template <bool IMG_IS_A, int NT>
+template <bool IMG_IS_A, bool FOLD, int NT>
 __device__ __forceinline__ void mm_tiles(const v4i (&lo)[NT], const v4i (&hi)[NT], const v4i (&w)[kMmDigits], const MmConst& K,
                                          MmAcc (&r)[NT]) {
   auto mm = [&](v4i img, v4i band, v4i c) -> v4i {
@@ -206,12 +223,12 @@ __device__ __forceinline__ void mm_tiles(const v4i (&lo)[NT], const v4i (&hi)[NT
 #pragma unroll
   for (int i = 0; i < NT; ++i) t3[i] = mm(hi[i], w[2], t3[i]);
 #pragma unroll
-  for (int i = 0; i < NT; ++i) t4[i] = mm(lo[i], w[4], (t3[i] >> 8) + K.c4);  // level 4
+  for (int i = 0; i < NT; ++i) t4[i] = mm(lo[i], w[4], mm_level4<FOLD>(t3[i]));  // level 4
 #pragma unroll
   for (int i = 0; i < NT; ++i) t4[i] = mm(hi[i], w[3], t4[i]);
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
-    r[i].v = mm(hi[i], w[4], t4[i] >> 8);                                      // level 5 = floor(T' / 2^40)
+    r[i].v = mm(hi[i], w[4], t4[i] >> 8);                                      // level 5 = floor(T' / 2^40) (FOLD: - kMmBias)
     r[i].z = (t3[i] | t4[i]) & 255;
   }
 }
@@ -270,9 +287,14 @@ __device__ __forceinline__ bool mm_wave_flat(const uint4& lo, const uint4& hi) {
   return __ballot(d != 0u) == 0ull;
 }
 
-// four outputs of a lane, branch-free: packed results and ONE flag (some output of the four is undecided)
+// Four outputs of a lane, branch-free: the results packed in 16-bit halves, and the SMALLEST of their decision bytes (0: some
+// output of the four is undecided; the caller folds the minima of its tiles into ONE test per pass).
+// int16 frames: the halves are the int16 results.  uint16 frames (chain with FOLD): the halves are floor(S) - kMmBias, and
+//   mm_pixels        adds 0x8080 back per half where pixels are stored: one packed add per register;
+//   mm_store_planes  takes the digit planes straight from them: the low byte of v - 0x8080 IS (v & 255) ^ 0x80, and the
+//                    high byte of (v - 0x8080) + 0x0080 = v - 0x8000 IS (v >> 8) ^ 0x80 -- one packed add per register, no xor.
 template <bool SIGNED>
-__device__ __forceinline__ uint2 mm_finish_flag(const MmAcc& r, bool& bad) {
+__device__ __forceinline__ uint2 mm_finish_flag(const MmAcc& r, unsigned& zmin) {
   unsigned v[4], z[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -282,9 +304,24 @@ __device__ __forceinline__ uint2 mm_finish_flag(const MmAcc& r, bool& bad) {
   }
   unsigned zm = z[0] < z[1] ? z[0] : z[1];
   zm = zm < z[2] ? zm : z[2];
-  zm = zm < z[3] ? zm : z[3];
-  bad = zm == 0u;
+  zmin = zm < z[3] ? zm : z[3];
   return uint2{__builtin_amdgcn_perm(v[1], v[0], 0x05040100u), __builtin_amdgcn_perm(v[3], v[2], 0x05040100u)};
+}
+template <bool SIGNED>
+__device__ __forceinline__ uint2 mm_pixels(uint2 res) {
+  return SIGNED ? res : uint2{pl_pk_add_u16(res.x, 0x80808080u), pl_pk_add_u16(res.y, 0x80808080u)};
+}
+// the lane's four results of an axis-0 tile into the two digit planes (lo at vd, hi at vd + hi_off)
+template <bool SIGNED>
+__device__ __forceinline__ void mm_store_planes(unsigned char* vd, int hi_off, uint2 res) {
+  if (SIGNED) {                                  // the signed high byte already is x_hi - 128
+    *reinterpret_cast<unsigned*>(vd) = __builtin_amdgcn_perm(res.y, res.x, 0x06040200u) ^ 0x80808080u;
+    *reinterpret_cast<unsigned*>(vd + hi_off) = __builtin_amdgcn_perm(res.y, res.x, 0x07050301u);
+  } else {
+    *reinterpret_cast<unsigned*>(vd) = __builtin_amdgcn_perm(res.y, res.x, 0x06040200u);
+    *reinterpret_cast<unsigned*>(vd + hi_off) =
+        __builtin_amdgcn_perm(pl_pk_add_u16(res.y, 0x00800080u), pl_pk_add_u16(res.x, 0x00800080u), 0x07050301u);
+  }
 }
 
 // ------------------------------------------------------------------ eight waves, ONE barrier per step
@@ -321,6 +358,7 @@ __global__ void __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(
 gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int strips, int segs, int seg_rows, const MmParams P) {
   constexpr bool kSigned = (T)-1 < (T)0;
   constexpr unsigned kHiFlip = kSigned ? 0u : 0x80808080u;     // int16: the signed high byte already is x_hi - 128
+  constexpr bool kFold = !kSigned;                             // uint16: the chain runs without kMmBias (mm_finish_flag)
   __shared__ __attribute__((aligned(16))) unsigned char s_mem[kGLds];
 
   unsigned id = pl_xcd_remap(blockIdx.x, gridDim.x);
@@ -362,8 +400,20 @@ gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int stri
   // vmcnt(0) after every load, four serialised round trips per row group instead of one group in flight for a whole step).
   // A quad ACROSS the right edge (w % 4 == 2: columns w - 2, w - 1 and their reflections) loads columns w - 4 .. w - 1 -- eight
   // bytes inside the frame -- and store_quad builds {w - 2, w - 1, w - 1, w - 2} from the upper half.
-  auto load_quad = [&](int k, FQuad& x) {
-    const int rbase = r_begin - kMmHalo + 16 * k + 4 * rq;
+  // A row group whose 16 rows all lie inside the frame (62 of a strip's 69 at 1024 rows) reflects nothing: its rows are
+  // wave-uniform and go into the load's SCALAR offset, the lane's offset is a loop invariant -- no vector instruction per
+  // load.  The range check sees the lane's offset alone: idle lanes keep theirs out of range, and a group that reaches
+  // beyond the frame takes the reflecting arithmetic (there the scalar offset is 0, so the check covers the whole address).
+  const unsigned off_in = loader ? 4u * (unsigned)rq * wb + colb_ld : 0x80000000u;
+  // (The prologue's five groups always reflect: a uniform branch per group there would only split its loads into blocks.)
+  auto load_quad = [&](int k, FQuad& x, bool may_be_inside) {
+    const int rb0 = r_begin - kMmHalo + 16 * k;
+    if (may_be_inside && rb0 >= 0 && rb0 + 16 <= h) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) x.r[i] = pl_buffer_load_u64(src, off_in, (unsigned)(rb0 + i) * wb);
+      return;
+    }
+    const int rbase = rb0 + 4 * rq;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       int r = rbase + i;
@@ -409,14 +459,14 @@ gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int stri
   for (int d = 0; d < kMmDigits; ++d) band[d] = mm_band_operand(P, d, lane);
   __builtin_amdgcn_s_waitcnt(0x0f70);              // vmcnt(0), expcnt / lgkmcnt untouched
   MmConst K = mm_const(P);
-  asm volatile("" : "+v"(K.c1), "+v"(K.c4));
+  asm volatile("" : "+v"(K.c1));
   // row groups 0 .. 3 go to LDS now, group 4 stays in flight: step s writes group s + 4 and loads group s + 5
   FQuad nxt;
   {
     FQuad a[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) load_quad(k, a[k]);
-    load_quad(4, nxt);
+    for (int k = 0; k < 4; ++k) load_quad(k, a[k], false);
+    load_quad(4, nxt, false);
 #pragma unroll
     for (int k = 0; k < 4; ++k) store_quad(k, a[k]);
   }
@@ -437,7 +487,6 @@ gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int stri
       auto run = [&](auto NT, int t0, int tstep) {
         constexpr int N = decltype(NT)::value;
         auto tile_of = [&](int i) { const int t = t0 + tstep * i; return t < nvt ? t : 0; };
-        unsigned badbits = 0;
         v4i lo[N], hi[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) {
@@ -447,17 +496,18 @@ gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int stri
           hi[i] = v4i{(int)qhi.x, (int)qhi.y, (int)qhi.z, (int)qhi.w};
         }
         MmAcc acc[N];
-        mm_tiles<true, N>(lo, hi, band, K, acc);
+        mm_tiles<true, kFold, N>(lo, hi, band, K, acc);
+        unsigned zm[N], zall = 0u;
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-          bool bad;
-          const uint2 res = mm_finish_flag<kSigned>(acc[i], bad);
-          badbits |= (bad && row_ok) ? (1u << i) : 0u;
-          unsigned char* vd = vout + 256 * tile_of(i);
-          *reinterpret_cast<unsigned*>(vd) = __builtin_amdgcn_perm(res.y, res.x, 0x06040200u) ^ 0x80808080u;
-          *reinterpret_cast<unsigned*>(vd + (kGVHi - kGVLo)) = __builtin_amdgcn_perm(res.y, res.x, 0x07050301u) ^ kHiFlip;
+          const uint2 res = mm_finish_flag<kSigned>(acc[i], zm[i]);
+          zall = (i == 0 || zm[i] < zall) ? zm[i] : zall;
+          mm_store_planes<kSigned>(vout + 256 * tile_of(i), kGVHi - kGVLo, res);
         }
-        if (__ballot(badbits != 0u) == 0ull) return;
+        if (__ballot(zall == 0u && row_ok) == 0ull) return;      // ONE test per pass: which tiles, only when some lane has one
+        unsigned badbits = 0;
+#pragma unroll
+        for (int i = 0; i < N; ++i) badbits |= (zm[i] == 0u && row_ok) ? (1u << i) : 0u;
         // ---- undecided outputs of the wave's tiles (rare): scipy's float64 sequence from the input plane bytes
         auto sample = [&](int x, int p) {          // window column x, plane row p (0 .. 63) of this step
           const int a = ((s + (p >> 4)) % kGSlots) * kFPlane + f_cell(x) + (p & 15);
@@ -476,7 +526,7 @@ gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int stri
             *reinterpret_cast<unsigned*>(vd) = (0x01010101u * (v & 255u)) ^ 0x80808080u;
             *reinterpret_cast<unsigned*>(vd + (kGVHi - kGVLo)) = (0x01010101u * (v >> 8)) ^ kHiFlip;
           } else {                                 // the tile once more (every lane): WHICH outputs are undecided
-            const MmAcc ra = mm_tile<true>(v4i{(int)flo.x, (int)flo.y, (int)flo.z, (int)flo.w}, v4i{(int)fhi.x, (int)fhi.y, (int)fhi.z, (int)fhi.w}, band, K);
+            const MmAcc ra = mm_tile<true, kFold>(v4i{(int)flo.x, (int)flo.y, (int)flo.z, (int)flo.w}, v4i{(int)fhi.x, (int)fhi.y, (int)fhi.z, (int)fhi.w}, band, K);
             if ((badbits >> i) & 1u) {
 #pragma unroll 1
               for (int q = 0; q < 4; ++q) {
@@ -496,7 +546,7 @@ gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int stri
     // W after the axis-0 tiles: the group loaded during the previous step (s + 4) has had a whole step to arrive, and the
     // output stores of the previous axis-1 pass, which the in-order vmcnt makes this wait for as well, an axis-0 pass
     store_quad(wslot, nxt);
-    load_quad(s + 5, nxt);
+    load_quad(s + 5, nxt, true);
     __syncthreads();
 
     // ---- axis 1: Toeplitz (M = output column) x image (N = row j): lane (j, g) gets columns 16 t + 4 g .. + 3 of row j
@@ -511,7 +561,7 @@ gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int stri
       };
       auto tile_of = [&](int i) { const int t = 2 * wave + i; return t < nht ? t : 0; };
       constexpr int N = 2;
-      unsigned badbits = 0;
+      unsigned zm0, zm1;
       auto hpass = [&](auto RAGGED) {
         v4i lo[N], hi[N];
 #pragma unroll
@@ -522,10 +572,9 @@ gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int stri
           hi[i] = v4i{(int)qhi.x, (int)qhi.y, (int)qhi.z, (int)qhi.w};
         }
         MmAcc acc[N];
-        mm_tiles<false, N>(lo, hi, band, K, acc);
-        bool bad0, bad1;
-        const uint2 r0 = mm_finish_flag<kSigned>(acc[0], bad0), r1 = mm_finish_flag<kSigned>(acc[1], bad1);
-        badbits |= ((bad0 && row_ok) ? 1u : 0u) | ((bad1 && row_ok) ? 2u : 0u);
+        mm_tiles<false, kFold, N>(lo, hi, band, K, acc);
+        const uint2 r0 = mm_pixels<kSigned>(mm_finish_flag<kSigned>(acc[0], zm0));
+        const uint2 r1 = mm_pixels<kSigned>(mm_finish_flag<kSigned>(acc[1], zm1));
         const auto sx = __builtin_amdgcn_permlane16_swap(r0.x, r1.x, false, false);
         const auto sy = __builtin_amdgcn_permlane16_swap(r0.y, r1.y, false, false);
         const unsigned tsel = (g & 1) ? (unsigned)tile_of(1) : (unsigned)tile_of(0);
@@ -537,7 +586,8 @@ gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int stri
         }
       };
       if (ragged) hpass(std::true_type{}); else hpass(std::false_type{});
-      if (__ballot(badbits != 0u) != 0ull) {
+      if (__ballot((zm0 < zm1 ? zm0 : zm1) == 0u && row_ok) != 0ull) {   // ONE test per pass, as in the axis-0 pass
+        const unsigned badbits = ((zm0 == 0u && row_ok) ? 1u : 0u) | ((zm1 == 0u && row_ok) ? 2u : 0u);
         // the fix-up stores overwrite addresses the pass has just stored from OTHER lanes of this wave: retire those first
         __builtin_amdgcn_s_waitcnt(0x0f70);        // vmcnt(0) (also retires the look-ahead loads: rare path)
         auto store_cut2 = [&](unsigned off, int x0, unsigned d0, unsigned d1) {   // 4 columns from x0, cut at the edge
@@ -559,10 +609,10 @@ gauss2d_mm(const T* __restrict__ in, T* __restrict__ out, int h, int w, int stri
             const unsigned v = (unsigned short)pl_from_double<T>(mm_exact([&](int) { return c; }, P));
             store_cut2(doff + 32u * (unsigned)t, 16 * t + 4 * g, v | (v << 16), v | (v << 16));
           } else {
-            const MmAcc ra = mm_tile<false>(v4i{(int)flo.x, (int)flo.y, (int)flo.z, (int)flo.w}, v4i{(int)fhi.x, (int)fhi.y, (int)fhi.z, (int)fhi.w}, band, K);
+            const MmAcc ra = mm_tile<false, kFold>(v4i{(int)flo.x, (int)flo.y, (int)flo.z, (int)flo.w}, v4i{(int)fhi.x, (int)fhi.y, (int)fhi.z, (int)fhi.w}, band, K);
             if ((badbits >> i) & 1u) {
-              bool dummy;
-              uint2 res = mm_finish_flag<kSigned>(ra, dummy);
+              unsigned dummy;
+              uint2 res = mm_pixels<kSigned>(mm_finish_flag<kSigned>(ra, dummy));   // pixels, as the pass stored them
 #pragma unroll 1
               for (int q = 0; q < 4; ++q) {
                 if (ra.z[q] != 0) continue;
@@ -616,6 +666,13 @@ int pl_gauss_mm2d_covers(const void* in, const void* out, int h, int w, int radi
   // dword-by-dword stores)
   if (radius < 1 || radius > kMmMaxRad || h < 64 || w < 64 || (w & 1) || (int64_t)h * w * 2 >= 0x7fff0000LL) return 0;
   return !((reinterpret_cast<uintptr_t>(in) & 3) || (reinterpret_cast<uintptr_t>(out) & 3));
+}
+
+// 1 when pl_gauss_mm2d_launch takes these taps (wts: HOST memory, 2 * radius + 1 of them): mm_make_params' verdict, host
+// arithmetic only
+int pl_gauss_mm2d_taps_covered(const double* wts, int radius) {
+  MmParams P;
+  return mm_make_params(wts, radius, P) ? 1 : 0;
 }
 
 // 0 = launched; -1 = shape / alignment / taps not covered (the caller runs the two passes).  wts: HOST memory.

@@ -82,6 +82,17 @@ __device__ __forceinline__ int pl_reflect(int i, int n) {
   return m >= n ? p - 1 - m : m;
 }
 
+// two independent 16-bit sums in one register (v_pk_add_u16): each half wraps on its own, no carry from the low half into
+// the high one.  The CPU emulator of the tests has no packed types: there the same result from 32-bit operations
+__device__ __forceinline__ unsigned pl_pk_add_u16(unsigned a, unsigned b) {
+#ifdef PL_HIPEMU
+  return ((a & 0x7fff7fffu) + (b & 0x7fff7fffu)) ^ ((a ^ b) & 0x80008000u);
+#else
+  typedef unsigned short pl_v2u16 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, (pl_v2u16)(__builtin_bit_cast(pl_v2u16, a) + __builtin_bit_cast(pl_v2u16, b)));
+#endif
+}
+
 // three-operand VALU median/min/max on 32-bit keys (the compiler only forms min3/max3 on its own)
 __device__ __forceinline__ unsigned pl_umed3(unsigned a, unsigned b, unsigned c) {
   unsigned r;
