@@ -34,19 +34,20 @@ the keyword they are refused as before.
 """
 from __future__ import annotations
 
-import io
 import struct
 import warnings
 import zipfile
 from dataclasses import dataclass
+from functools import partial
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import PL_F32, PL_F64, PL_I16, PL_I32, PL_U8, PL_U16, check
-from ._stack_io import bytes_tensor, index_tensor, on_device
+from ._stack_io import bytes_tensor, index_tensor, on_device, source_bytes
 from .geometry import Point
 
 MM_PER_INCH = 25.4
@@ -237,14 +238,7 @@ def read_part10(source, jpeg_lossless: bool = False) -> tuple[Metadata, np.ndarr
     ``metadata.PixelDataFragments`` the list of (offset, length) of the fragments.  ``jpeg_lossless=True`` walks the items of
     the two JPEG Lossless syntaxes (``JPEG_LOSSLESS``) the same way; ``metadata.PixelDataOffsetTable`` is then the Basic
     Offset Table (a list, empty or one entry per frame).  Without it they are refused like every other encapsulated syntax."""
-    if isinstance(source, (bytes, bytearray, memoryview, np.ndarray)):
-        data = np.frombuffer(bytes(source) if not isinstance(source, np.ndarray) else source.tobytes(), dtype=np.uint8)
-    elif isinstance(source, (str, Path)):
-        data = np.fromfile(str(source), dtype=np.uint8)
-    else:
-        if isinstance(source, io.IOBase) or hasattr(source, "seek"):
-            source.seek(0)
-        data = np.frombuffer(source.read(), dtype=np.uint8)
+    data = np.frombuffer(source_bytes(source), dtype=np.uint8)
     return _walk_part10(memoryview(data).cast("B"), jpeg_lossless=jpeg_lossless), data
 
 
@@ -324,9 +318,26 @@ def _walk_elements(buf: memoryview, n: int, size, whole: bool, jpeg_lossless: bo
     return Metadata(values)
 
 
-def _layout(meta: Metadata):
-    """pydicom.pixel_data_handlers.util.pixel_dtype + get_expected_length for native data -> (torch container dtype, numpy
-    dtype string, PL code, bytes per sample, frames, rows, cols, big_endian, (offset, length) of the value)."""
+_CONTAINERS = {(8, 0): torch.uint8, (8, 1): torch.int8, (16, 0): torch.uint16, (16, 1): torch.int16, (32, 0): torch.uint32,
+               (32, 1): torch.int32}
+
+
+class _Layout(NamedTuple):
+    container: torch.dtype
+    sample_bytes: int
+    frames: int
+    rows: int
+    cols: int
+    big_endian: bool
+    value: tuple                                             # (offset, length) of the Pixel Data value; length -1: encapsulated
+
+    @property
+    def format(self):                                        # what the files of one stack must agree in
+        return self.container, self.rows, self.cols, self.big_endian
+
+
+def _layout(meta: Metadata) -> _Layout:
+    """pydicom.pixel_data_handlers.util.pixel_dtype + get_expected_length for native data."""
     for need in ("BitsAllocated", "Rows", "Columns", "PixelRepresentation", "SamplesPerPixel"):
         if need not in meta:
             raise AttributeError(f"Unable to convert the pixel data as the following required elements are missing from the dataset: {need}")
@@ -342,12 +353,8 @@ def _layout(meta: Metadata):
     if rep not in (0, 1):
         raise ValueError(f"Unable to determine the data type to use to contain the Pixel Data as a value of '{rep}' for "
                          "'(0028,0103) Pixel Representation' is invalid")
-    tdt = {(8, 0): torch.uint8, (8, 1): torch.int8, (16, 0): torch.uint16, (16, 1): torch.int16, (32, 0): torch.uint32,
-           (32, 1): torch.int32}[(bits, rep)]
-    code = {8: PL_U8, 16: PL_I16 if rep else PL_U16, 32: PL_I32}[bits]
-    frames = int(meta.get("NumberOfFrames") or 1)
-    big = meta.get("TransferSyntaxUID") == EXPLICIT_BE
-    return tdt, code, bits // 8, frames, int(meta.Rows), int(meta.Columns), big, meta.PixelData
+    return _Layout(_CONTAINERS[(bits, rep)], bits // 8, int(meta.get("NumberOfFrames") or 1), int(meta.Rows), int(meta.Columns),
+                   meta.get("TransferSyntaxUID") == EXPLICIT_BE, meta.PixelData)
 
 
 _NP_TO_TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
@@ -365,15 +372,14 @@ def decode_frames(file_bytes, offsets, rows: int, cols: int, bits_allocated: int
     buf = buf.to(device=dev, dtype=torch.uint8).contiguous()
     offs = index_tensor(offsets, torch.int64, dev)
     n = int(offs.numel())
-    rep = int(pixel_representation)
-    cont = {(8, 0): torch.uint8, (8, 1): torch.int8, (16, 0): torch.uint16, (16, 1): torch.int16, (32, 0): torch.uint32,
-            (32, 1): torch.int32}[(int(bits_allocated), rep)]
-    code = {8: PL_U8, 16: PL_I16 if rep else PL_U16, 32: PL_I32}[int(bits_allocated)]
-    odt, ocode = {"container": (cont, code), "float32": (torch.float32, PL_F32), "float64": (torch.float64, PL_F64)}[out]
+    bits, rep = int(bits_allocated), int(pixel_representation)
+    code = {8: PL_U8, 16: PL_I16 if rep else PL_U16, 32: PL_I32}[bits]
+    odt, ocode = {"container": (_CONTAINERS[(bits, rep)], code), "float32": (torch.float32, PL_F32),
+                  "float64": (torch.float64, PL_F64)}[out]
     res = torch.empty((n, rows, cols), dtype=odt, device=dev)
     status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
     slope, intercept = (float(rescale[0]), float(rescale[1])) if rescale is not None else (1.0, 0.0)
-    check(_lib.load().pl_dicom_decode(buf.data_ptr(), buf.numel(), offs.data_ptr(), n, rows, cols, int(bits_allocated),
+    check(_lib.load().pl_dicom_decode(buf.data_ptr(), buf.numel(), offs.data_ptr(), n, rows, cols, bits,
                                       int(bits_stored), rep, int(bool(big_endian)), int(bool(correct_unused_bits)), res.data_ptr(),
                                       ocode, int(rescale is not None), slope, intercept, status.data_ptr(),
                                       torch.cuda.current_stream(dev).cuda_stream), "pl_dicom_decode")
@@ -396,8 +402,6 @@ def decode_rle_frames(file_bytes, seg_off, seg_len, rows: int, cols: int, bits_a
     [N, rows * cols * BitsAllocated / 8] to decode into."""
     dev = on_device(device)
     bits, rep = int(bits_allocated), int(pixel_representation)
-    cont = {(8, 0): torch.uint8, (8, 1): torch.int8, (16, 0): torch.uint16, (16, 1): torch.int16, (32, 0): torch.uint32,
-            (32, 1): torch.int32}[(bits, rep)]
     segments = bits // 8
     if max_segment_bytes is None:
         max_segment_bytes = int(seg_len.max()) if isinstance(seg_len, torch.Tensor) else int(np.max(seg_len, initial=0))
@@ -407,11 +411,7 @@ def decode_rle_frames(file_bytes, seg_off, seg_len, rows: int, cols: int, bits_a
     n = int(so.shape[0])
     if so.shape != sl.shape:
         raise ValueError("decode_rle_frames: seg_off and seg_len must both be [N, BitsAllocated / 8]")
-    frame_bytes = rows * cols * segments
-    if native is None:
-        native = torch.empty((n, frame_bytes), dtype=torch.uint8, device=dev)
-    elif native.dtype != torch.uint8 or tuple(native.shape) != (n, frame_bytes) or not native.is_contiguous() or not native.is_cuda:
-        raise ValueError("decode_rle_frames: native must be a contiguous uint8 device tensor [N, rows * cols * BitsAllocated / 8]")
+    native = _native_buffer(native, n, rows * cols * segments, dev, "decode_rle_frames")
     lib = _lib.load()
     nwork = int(lib.pl_dicom_rle_work_bytes(n, segments, int(max_segment_bytes)))
     work = torch.empty(max(nwork, 16), dtype=torch.uint8, device=dev)
@@ -419,17 +419,26 @@ def decode_rle_frames(file_bytes, seg_off, seg_len, rows: int, cols: int, bits_a
     check(lib.pl_dicom_rle_decode(buf.data_ptr(), buf.numel(), so.data_ptr(), sl.data_ptr(), n, segments, int(max_segment_bytes),
                                   rows, cols, native.data_ptr(), status.data_ptr(), work.data_ptr(),
                                   torch.cuda.current_stream(dev).cuda_stream), "pl_dicom_rle_decode")
-    return _from_native(native, status[:n], cont, rows, cols, bits, bits_stored, rep, correct_unused_bits, out, rescale, dev)
+    return _from_native(native, status[:n], rows, cols, bits, bits_stored, rep, correct_unused_bits, out, rescale, dev)
 
 
-def _from_native(native: torch.Tensor, status: torch.Tensor, cont, rows: int, cols: int, bits: int, bits_stored, rep: int,
+def _native_buffer(native, n: int, frame_bytes: int, dev, who: str) -> torch.Tensor:
+    """the ``native=`` argument of the two encapsulated decodes, validated under ``who``'s name; None: allocated"""
+    if native is None:
+        return torch.empty((n, frame_bytes), dtype=torch.uint8, device=dev)
+    if native.dtype != torch.uint8 or tuple(native.shape) != (n, frame_bytes) or not native.is_contiguous() or not native.is_cuda:
+        raise ValueError(f"{who}: native must be a contiguous uint8 device tensor [N, rows * cols * BitsAllocated / 8]")
+    return native
+
+
+def _from_native(native: torch.Tensor, status: torch.Tensor, rows: int, cols: int, bits: int, bits_stored, rep: int,
                  correct_unused_bits: bool, out: str, rescale, dev) -> torch.Tensor:
     """The tail the RLE and the JPEG Lossless decodes share: the decoded little-endian buffer [N, frame bytes] -> [N, rows,
     cols] -- a view for the plain container dtype, through ``pl_dicom_decode`` otherwise -- carrying ``status``."""
     n, frame_bytes = int(native.shape[0]), int(native.shape[1])
     stored = bits if bits_stored is None else int(bits_stored)
     if out == "container" and not (correct_unused_bits and stored < bits):
-        res = native.view(cont).reshape(n, rows, cols)
+        res = native.view(_CONTAINERS[(bits, rep)]).reshape(n, rows, cols)
     else:
         res = decode_frames(native.reshape(-1), torch.arange(n, dtype=torch.int64, device=dev) * frame_bytes, rows, cols, bits,
                             stored, rep, big_endian=False, correct_unused_bits=correct_unused_bits, out=out, rescale=rescale,
@@ -480,11 +489,6 @@ def _jpegll_refusals(ib: int, cols: int) -> None:
     _jpegll_cols(cols)
 
 
-def _rle_fragment_count(found: list, frames: int, name: str) -> None:
-    if len(found) != frames:
-        raise ValueError(f"{name}: {len(found)} RLE fragments for NumberOfFrames = {frames} (one fragment per frame)")
-
-
 def decode_jpeg_lossless_frames(file_bytes, scan_off, scan_len, params, huff, rows: int, cols: int, bits_allocated: int,
                                 bits_stored: int | None = None, pixel_representation: int = 0, correct_unused_bits: bool = False,
                                 out: str = "container", rescale=None, device=None,
@@ -505,7 +509,6 @@ def decode_jpeg_lossless_frames(file_bytes, scan_off, scan_len, params, huff, ro
     bits, rep = int(bits_allocated), int(pixel_representation)
     if bits not in (8, 16):
         raise ValueError("decode_jpeg_lossless_frames: BitsAllocated 8 or 16")
-    cont = {(8, 0): torch.uint8, (8, 1): torch.int8, (16, 0): torch.uint16, (16, 1): torch.int16}[(bits, rep)]
     buf = bytes_tensor(file_bytes, dev)
     so, sl = index_tensor(scan_off, torch.int64, dev).reshape(-1), index_tensor(scan_len, torch.int64, dev).reshape(-1)
     n = int(so.numel())
@@ -513,12 +516,7 @@ def decode_jpeg_lossless_frames(file_bytes, scan_off, scan_len, params, huff, ro
     tab = bytes_tensor(huff, dev).reshape(-1, 33)
     if not (sl.numel() == par.shape[0] == tab.shape[0] == n):
         raise ValueError("decode_jpeg_lossless_frames: scan_off and scan_len [N], params [N, 4] and huff [N, 33] must agree in N")
-    frame_bytes = rows * cols * (bits // 8)
-    if native is None:
-        native = torch.empty((n, frame_bytes), dtype=torch.uint8, device=dev)
-    elif native.dtype != torch.uint8 or tuple(native.shape) != (n, frame_bytes) or not native.is_contiguous() or not native.is_cuda:
-        raise ValueError("decode_jpeg_lossless_frames: native must be a contiguous uint8 device tensor "
-                         "[N, rows * cols * BitsAllocated / 8]")
+    native = _native_buffer(native, n, rows * cols * (bits // 8), dev, "decode_jpeg_lossless_frames")
     lib = _lib.load()
     nwork = int(lib.pl_dicom_jpegll_work_bytes(n, rows, cols))
     work = torch.empty(max(nwork, 16), dtype=torch.uint8, device=dev)
@@ -526,7 +524,7 @@ def decode_jpeg_lossless_frames(file_bytes, scan_off, scan_len, params, huff, ro
     check(lib.pl_dicom_jpegll_decode(buf.data_ptr(), buf.numel(), so.data_ptr(), sl.data_ptr(), par.data_ptr(), tab.data_ptr(), n,
                                      rows, cols, bits // 8, native.data_ptr(), status.data_ptr(), work.data_ptr(),
                                      torch.cuda.current_stream(dev).cuda_stream), "pl_dicom_jpegll_decode")
-    return _from_native(native, status[:n], cont, rows, cols, bits, bits_stored, rep, correct_unused_bits, out, rescale, dev)
+    return _from_native(native, status[:n], rows, cols, bits, bits_stored, rep, correct_unused_bits, out, rescale, dev)
 
 
 _SOF_REFUSED = {0xC0: "SOF0 (baseline DCT)", 0xC1: "SOF1 (extended sequential DCT)", 0xC2: "SOF2 (progressive DCT)",
@@ -680,16 +678,99 @@ def _check_jpegll_status(status: torch.Tensor, owner, names) -> None:
         raise ValueError(f"{names[owner[k]]}, frame {k} of the stack: JPEG Lossless Pixel Data: {why}")
 
 
-def _check_status(frames: torch.Tensor) -> torch.Tensor:
-    st = getattr(frames, "_pl_status", None)
-    if st is not None and bool(st.any()):
+def _check_native_status(status: torch.Tensor, owner=None, names=None) -> None:
+    if bool(status.any()):
         raise ValueError("The length of the pixel data in the dataset doesn't match the expected length; the dataset may be "
                          "corrupted")
+
+
+def _check_status(frames: torch.Tensor) -> torch.Tensor:
+    st = getattr(frames, "_pl_status", None)
+    if st is not None:
+        _check_native_status(st)
     return frames
 
 
 _MIXED_JPEGLL = "load_frames: JPEG Lossless files are mixed with native or RLE Lossless files; load the kinds separately"
 _MIXED_RLE = "load_frames: native and RLE Lossless files are mixed; load the two kinds separately"
+_DECODERS = {"native": (decode_frames, _check_native_status), "rle": (decode_rle_frames, _check_rle_status),
+             "jpegll": (decode_jpeg_lossless_frames, _check_jpegll_status)}
+
+
+def _frame_plan(metas, who: str, noun: str):
+    """What ``load_frames`` (``noun``: files) and ``load_zip`` (members) settle as soon as the headers are parsed, before a
+    fragment is looked at: one pixel format and frame size, one kind -> (kind "native" | "rle" | "jpegll", the layouts, and
+    for native data the file of every frame and the frame's offset inside that file)."""
+    lay = [_layout(m) for m in metas]
+    first = lay[0]
+    for l in lay[1:]:
+        if l.format != first.format:
+            raise ValueError(f"{who}: the {noun} differ in pixel format or frame size (the reference's stacks refuse that too)")
+    kinds = {"native" if m.PixelData[1] >= 0 else "rle" if m.TransferSyntaxUID == RLE_LOSSLESS else "jpegll" for m in metas}
+    if len(kinds) > 1:
+        raise ValueError(_MIXED_JPEGLL if "jpegll" in kinds else _MIXED_RLE)
+    owner, inside = [], []
+    if kinds == {"native"}:
+        frame_bytes = first.rows * first.cols * first.sample_bytes
+        for k, l in enumerate(lay):
+            off, ln = l.value
+            if ln < l.frames * frame_bytes:
+                raise ValueError(f"The length of the pixel data in the dataset ({ln} bytes) "
+                                 f"doesn't match the expected length ({l.frames * frame_bytes} bytes). "
+                                 "The dataset may be corrupted or there may be an issue with the pixel data handler.")
+            owner += [k] * l.frames
+            inside += [off + f * frame_bytes for f in range(l.frames)]
+    return kinds.pop(), lay, owner, np.asarray(inside, dtype=np.int64)
+
+
+def _rle_windows(metas, lay, names, base, head):
+    """The segments of every RLE frame (one fragment per frame, PS3.5 section A.4.2) -> (seg_off, seg_len as
+    ``decode_rle_frames`` takes them, the file of every frame).  ``base[k]``: where file k begins in the buffer that is
+    decoded; ``head(k, j)``: the first 64 bytes of its fragment j."""
+    windows, owner = [], []
+    for k, (meta, l) in enumerate(zip(metas, lay)):
+        found = meta.PixelDataFragments
+        if len(found) != l.frames:
+            raise ValueError(f"{names[k]}: {len(found)} RLE fragments for NumberOfFrames = {l.frames} (one fragment per frame)")
+        for j, frag in enumerate(found):
+            windows.append([(int(base[k]) + o, n) for o, n in _rle_segments(head(k, j), frag, l.sample_bytes, names[k])])
+            owner.append(k)
+    windows = np.asarray(windows, dtype=np.int64).reshape(-1, lay[0].sample_bytes, 2)
+    return np.ascontiguousarray(windows[:, :, 0]), np.ascontiguousarray(windows[:, :, 1]), owner
+
+
+def _jpegll_tables(scans: list):
+    """[(file, where the frame's stream begins in the buffer that is decoded, ``_jpegll_header``'s answer for it)] per frame
+    -> ((scan_off, scan_len, params, huff) as ``decode_jpeg_lossless_frames`` takes them, the file of every frame)"""
+    tables = (np.asarray([at + h[0] for _, at, h in scans], dtype=np.int64),
+              np.asarray([h[1] for _, _, h in scans], dtype=np.int64),
+              np.asarray([h[2] for _, _, h in scans], dtype=np.int32).reshape(-1, 4),
+              np.stack([np.frombuffer(h[3], dtype=np.uint8) for _, _, h in scans]))
+    return tables, [k for k, _, _ in scans]
+
+
+def _decode_keywords(l: _Layout, meta: Metadata, correct_unused_bits: bool, device) -> dict:
+    """the keywords the three decodes share, for a stack of layout ``l`` whose first file's metadata are ``meta``"""
+    bits = l.sample_bytes * 8
+    return dict(rows=l.rows, cols=l.cols, bits_allocated=bits, bits_stored=int(meta.get("BitsStored") or bits),
+                pixel_representation=int(meta.PixelRepresentation), correct_unused_bits=correct_unused_bits, device=device)
+
+
+def _decode_step(kind: str, buffer, where: tuple, l: _Layout, meta: Metadata, correct_unused_bits: bool, device):
+    """-> decode(out=..., rescale=...) = (frames, status) for ``_finish_frames``: the decode of ``kind`` over ``buffer``,
+    ``where`` being the arrays that place the frames in it (frame offsets | seg_off, seg_len | scan_off, scan_len, params,
+    huff)."""
+    common = _decode_keywords(l, meta, correct_unused_bits, device)
+    if kind == "native":
+        common["big_endian"] = l.big_endian
+    elif kind == "rle":
+        common["max_segment_bytes"] = int(where[1].max(initial=0))
+
+    def decode(**kw):
+        x = _DECODERS[kind][0](buffer, *where, **common, **kw)
+        return x, x._pl_status
+
+    return decode
 
 
 def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bool | None = None,
@@ -712,124 +793,50 @@ def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bo
         m, b = read_part10(s, jpeg_lossless=jpeg_lossless)
         metas.append(m)
         blobs.append(b)
-    lay = [_layout(m) for m in metas]
-    tdt, code, ib, _, rows, cols, big, _ = lay[0]
-    for l in lay[1:]:
-        if (l[0], l[4], l[5], l[6]) != (tdt, rows, cols, big):
-            raise ValueError("load_frames: the files differ in pixel format or frame size (the reference's stacks refuse that too)")
     names = [f"file {k}" + (f" ({s})" if isinstance(s, (str, Path)) else "") for k, s in enumerate(sources)]
-    kinds = {"jpegll" if "PixelDataOffsetTable" in m else "rle" if "PixelDataFragments" in m else "native" for m in metas}
-    if "jpegll" in kinds:
-        if len(kinds) > 1:
-            raise ValueError(_MIXED_JPEGLL)
-        return _load_jpegll(metas, blobs, lay, names, dtype, raw_pixels, invert_pixels, correct_unused_bits, device, check), metas
-    rle = ["PixelDataFragments" in m for m in metas]
-    if any(rle) and not all(rle):
-        raise ValueError(_MIXED_RLE)
-    rle = all(rle) and bool(metas)
-    # one host buffer, every file at a 4-byte boundary; frame offsets (RLE: segment windows) inside it
-    starts, offsets, owner, pos = [], [], [], 0
-    for k, (b, l) in enumerate(zip(blobs, lay)):
-        starts.append(pos)
-        off, ln = l[7]
-        frames = l[3]
-        if rle:
-            found = metas[k].PixelDataFragments
-            _rle_fragment_count(found, frames, names[k])
-            for frag in found:
-                offsets.append([(pos + o, n) for o, n in _rle_segments(b[frag[0]:frag[0] + 64], frag, ib, names[k])])
-                owner.append(k)
-            pos += (len(b) + 3) & ~3
-            continue
-        expected = frames * rows * cols * ib
-        if ln < expected:
-            raise ValueError(f"The length of the pixel data in the dataset ({ln} bytes) doesn't match the expected length "
-                             f"({expected} bytes). The dataset may be corrupted or there may be an issue with the pixel data handler.")
-        for f in range(frames):
-            offsets.append(pos + off + f * rows * cols * ib)
-            owner.append(k)
-        pos += (len(b) + 3) & ~3
-    host = np.zeros(pos, dtype=np.uint8)
-    for st, b in zip(starts, blobs):
-        host[st:st + len(b)] = b
-    stored = int(metas[0].get("BitsStored") or ib * 8)
-    rep = int(metas[0].PixelRepresentation)
-    common = dict(rows=rows, cols=cols, bits_allocated=ib * 8, bits_stored=stored, pixel_representation=rep, big_endian=big,
-                  correct_unused_bits=correct_unused_bits, device=device)
-    if rle:                                                  # the same calls, the RLE kernels in front of pl_dicom_decode
-        del common["big_endian"]
-        windows = np.asarray(offsets, dtype=np.int64).reshape(-1, ib, 2)
-        seg_off, seg_len = np.ascontiguousarray(windows[:, :, 0]), np.ascontiguousarray(windows[:, :, 1])
-
-        seen = []
-
-        def decode(**kw):
-            x = decode_rle_frames(host, seg_off, seg_len, max_segment_bytes=int(seg_len.max(initial=0)), **common, **kw)
-            seen.append(x._pl_status)                        # (an integer astype hands on a tensor without it)
-            return x
-
-        def verify(x):
-            _check_rle_status(seen[-1], owner, names)
-            return x
-    else:
-        def decode(**kw):
-            return decode_frames(host, offsets, **common, **kw)
-
-        verify = _check_status
-    return _finish_frames(decode, verify, metas, owner, rows, cols, dtype, raw_pixels, invert_pixels, check), metas
-
-
-def _load_jpegll(metas, blobs, lay, names, dtype, raw_pixels: bool, invert_pixels, correct_unused_bits: bool, device, check: bool):
-    """``load_frames`` for JPEG Lossless files: every frame's fragment payloads end to end at a 4-byte boundary of one host
-    buffer (the kernel sees one window per frame), its markers parsed where they lie, then the tail every kind shares."""
-    _, _, ib, _, rows, cols, _, _ = lay[0]
-    host, tables, owner = _jpegll_stage(metas, blobs, lay, names)
-    stored = int(metas[0].get("BitsStored") or ib * 8)
-    common = dict(rows=rows, cols=cols, bits_allocated=ib * 8, bits_stored=stored,
-                  pixel_representation=int(metas[0].PixelRepresentation), correct_unused_bits=correct_unused_bits, device=device)
-    seen = []
-
-    def decode(**kw):
-        x = decode_jpeg_lossless_frames(host, *tables, **common, **kw)
-        seen.append(x._pl_status)                            # (an integer astype hands on a tensor without it)
-        return x
-
-    def verify(x):
-        _check_jpegll_status(seen[-1], owner, names)
-        return x
-
-    return _finish_frames(decode, verify, metas, owner, rows, cols, dtype, raw_pixels, invert_pixels, check)
+    kind, lay, owner, inside = _frame_plan(metas, "load_frames", "files")
+    if kind == "jpegll":
+        host, where, owner = _jpegll_stage(metas, blobs, lay, names)
+    else:                                                    # one host buffer, every file at a 4-byte boundary
+        starts = np.cumsum([0] + [(len(b) + 3) & ~3 for b in blobs])
+        if kind == "rle":
+            *where, owner = _rle_windows(metas, lay, names, starts,
+                                         lambda k, j: blobs[k][metas[k].PixelDataFragments[j][0]:][:64])
+        else:
+            where = (starts[owner] + inside,)
+        host = np.zeros(starts[-1], dtype=np.uint8)
+        for st, b in zip(starts, blobs):
+            host[st:st + len(b)] = b
+    decode = _decode_step(kind, host, where, lay[0], metas[0], correct_unused_bits, device)
+    verify = partial(_DECODERS[kind][1], owner=owner, names=names)
+    return _finish_frames(decode, verify, metas, owner, lay[0].rows, lay[0].cols, dtype, raw_pixels, invert_pixels, check), metas
 
 
 def _jpegll_stage(metas, blobs, lay, names):
-    """The host side of a JPEG Lossless stack -> (the staging buffer, (scan_off, scan_len, params, huff) as
-    ``decode_jpeg_lossless_frames`` takes them, the file of every frame); every refusal of a file happens here."""
-    _, _, ib, _, rows, cols, _, _ = lay[0]
+    """The host side of a JPEG Lossless stack: every frame's fragment payloads end to end at a 4-byte boundary of one host
+    buffer (the kernel sees one window per frame), its markers parsed where they lie -> (the staging buffer, (scan_off,
+    scan_len, params, huff) as ``decode_jpeg_lossless_frames`` takes them, the file of every frame); every refusal of a file
+    happens here."""
+    rows, cols, ib = lay[0].rows, lay[0].cols, lay[0].sample_bytes
     _jpegll_refusals(ib, cols)
-    pieces, owner, scan_off, scan_len, params, huff, pos = [], [], [], [], [], [], 0
+    pieces, scans, pos = [], [], 0
     for k, (m, b, l) in enumerate(zip(metas, blobs, lay)):
-        for frags in _jpegll_frames(m, l[3], names[k]):
+        for frags in _jpegll_frames(m, l.frames, names[k]):
             data = b[frags[0][0]:frags[0][0] + frags[0][1]] if len(frags) == 1 else np.concatenate([b[o:o + n] for o, n in frags])
-            start, length, par, table = _jpegll_header(data, rows, cols, ib * 8, names[k])
+            scans.append((k, pos, _jpegll_header(data, rows, cols, ib * 8, names[k])))
             pieces.append((pos, data))
-            owner.append(k)
-            scan_off.append(pos + start)
-            scan_len.append(length)
-            params.append(par)
-            huff.append(np.frombuffer(table, dtype=np.uint8))
             pos += (len(data) + 3) & ~3
     host = np.zeros(pos, dtype=np.uint8)
     for at, data in pieces:
         host[at:at + len(data)] = data
-    tables = (np.asarray(scan_off, dtype=np.int64), np.asarray(scan_len, dtype=np.int64), np.asarray(params, dtype=np.int32),
-              np.stack(huff))
-    return host, tables, owner
+    return (host,) + _jpegll_tables(scans)
 
 
 def _finish_frames(decode, verify, metas, owner, rows: int, cols: int, dtype, raw_pixels: bool, invert_pixels, check: bool):
-    """The tail ``load_frames`` and ``load_zip`` share: ``decode(out=..., rescale=...)`` is the device decode of every frame,
-    ``verify(x)`` raises for a flagged one; the dtype rules, the rescale (fused when every file carries the same tags, file by
-    file otherwise) and the inversion of ``DicomImage.__init__``."""
+    """The tail ``load_frames`` and ``load_zip`` share: ``decode(out=..., rescale=...)`` is the device decode of every frame
+    -> (frames, per-frame status), ``verify(status)`` raises for a flagged one; the dtype rules, the rescale (fused when every
+    file carries the same tags, file by file otherwise) and the inversion of ``DicomImage.__init__``.  The frames returned
+    carry the status as ``_pl_status``."""
     from .image import rescale_dicom_values
 
     has_rescale = [("RescaleSlope" in m and "RescaleIntercept" in m) for m in metas]
@@ -837,24 +844,24 @@ def _finish_frames(decode, verify, metas, owner, rows: int, cols: int, dtype, ra
     inverts = [bool(invert_pixels or (invert_pixels is None and m.get("PixelIntensityRelationshipSign") == -1)) for m in metas]
     np_dt = None if dtype is None else np.dtype(dtype)
     if raw_pixels or not any(has_rescale):
-        if np_dt is None:
-            x = decode(out="container")
-        elif np_dt in _NP_TO_TORCH:
-            x = decode(out={4: "float32", 8: "float64"}[np_dt.itemsize])
+        if np_dt in _NP_TO_TORCH:
+            x, status = decode(out={4: "float32", 8: "float64"}[np_dt.itemsize])
         else:
-            x = _astype(decode(out="container"), np_dt)
+            x, status = decode(out="container")
+            if np_dt is not None:
+                x = _astype(x, np_dt)
         if check:
-            verify(x)
+            verify(status)
     elif same and np_dt in (None, np.dtype(np.float64)):
-        x = decode(out="float64", rescale=(metas[0].RescaleSlope, metas[0].RescaleIntercept))
+        x, status = decode(out="float64", rescale=(metas[0].RescaleSlope, metas[0].RescaleIntercept))
         if check:
-            verify(x)
+            verify(status)
     else:
         if not all(has_rescale):
             raise ValueError("load_frames: some files carry rescale tags and some do not; load them separately")
-        base = decode(out="container")
+        base, status = decode(out="container")
         if check:
-            verify(base)
+            verify(status)
         if np_dt is not None:
             base = _astype(base, np_dt)
         own = np.asarray(owner)
@@ -879,6 +886,7 @@ def _finish_frames(decode, verify, metas, owner, rows: int, cols: int, dtype, ra
                 idx = np.flatnonzero(own == k)
                 a, b = int(idx[0]), int(idx[-1]) + 1
                 x[a:b] = ops.invert(x[a:b].reshape(1, (b - a) * rows, cols)).reshape(b - a, rows, cols)
+    x._pl_status = status
     return x
 
 
@@ -889,7 +897,7 @@ def _member_header(raw, member, what: str, encapsulated: bool = False):
     reaches the (7FE0,0010) element header or the member ends.  ``encapsulated``: ``_walk_part10``'s."""
     import zlib
 
-    def walk(view, size):                                   # (the default path calls _walk_part10 as it always did)
+    def walk(view, size):                                   # (the keyword only when set: the default call stays (view, size))
         return _walk_part10(view, size, encapsulated=True) if encapsulated else _walk_part10(view, size)
 
     if member.size < 132:
@@ -947,7 +955,7 @@ def load_zip(source, members=None, verify: bool = True, dtype=None, raw_pixels: 
 
     archive, what, host, dbuf = zipstack.stage(source, device)
     hv = host.numpy()
-    taken, metas = [], []
+    taken, metas, labels = [], [], []
     for m in zipstack._select(archive, members, what):
         name = f"{what}: member {m.name!r}"
         try:
@@ -960,43 +968,31 @@ def load_zip(source, members=None, verify: bool = True, dtype=None, raw_pixels: 
             raise ValueError(f"{name}: not a DICOM Part-10 file (no DICM at byte 128)")
         taken.append(m)
         metas.append(meta)
+        labels.append(name)
     if not taken:
         raise ValueError(f"{what}: no DICOM members")
-    names = [m.name for m in taken]
-    lay = [_layout(m) for m in metas]
-    tdt, code, ib, _, rows, cols, big, _ = lay[0]
-    for l in lay[1:]:
-        if (l[0], l[4], l[5], l[6]) != (tdt, rows, cols, big):
-            raise ValueError("load_zip: the members differ in pixel format or frame size (the reference's stacks refuse that too)")
-    kinds = {"native" if m.PixelData[1] >= 0 else "rle" if m.TransferSyntaxUID == RLE_LOSSLESS else "jpegll" for m in metas}
-    if len(kinds) > 1:                                      # (load_frames's rule, in its words)
-        raise ValueError(_MIXED_JPEGLL if "jpegll" in kinds else _MIXED_RLE)
-    if kinds != {"native"}:
-        x = _load_zip_encapsulated(kinds.pop(), taken, metas, lay, what, host, dbuf, verify, check, dtype, raw_pixels,
-                                   invert_pixels, correct_unused_bits)
-        return x, metas, names
-    inside, owner = [], []                                  # frame offsets inside each member
-    for k, (m, l) in enumerate(zip(taken, lay)):
-        off, ln = l[7]
-        expected = l[3] * rows * cols * ib
-        if ln < expected:
-            raise ValueError(f"The length of the pixel data in the dataset ({ln} bytes) doesn't match the expected length "
-                             f"({expected} bytes). The dataset may be corrupted or there may be an issue with the pixel data handler.")
-        for f in range(l[3]):
-            inside.append(off + f * rows * cols * ib)
-            owner.append(k)
+    kind, lay, owner, inside = _frame_plan(metas, "load_zip", "members")
+    if kind == "jpegll":
+        _jpegll_refusals(lay[0].sample_bytes, lay[0].cols)
     stack = zipstack.run(taken, what, host, dbuf, verify=verify, check=check)
-    offsets = stack.offsets[np.asarray(owner)] + np.asarray(inside, dtype=np.int64)
-    stored = int(metas[0].get("BitsStored") or ib * 8)
-    common = dict(rows=rows, cols=cols, bits_allocated=ib * 8, bits_stored=stored,
-                  pixel_representation=int(metas[0].PixelRepresentation), big_endian=big, correct_unused_bits=correct_unused_bits,
-                  device=stack.buffer.device)
+    copied = None
+    if kind == "jpegll":
+        decode, owner, copied = _zip_jpegll_decode(stack, metas, lay, labels, correct_unused_bits)
+    else:
+        if kind == "rle":
+            heads = _index_members(stack, metas, lay, labels, False)
+            *where, owner = _rle_windows(metas, lay, labels, stack.offsets, lambda k, j: heads[k][j])
+        else:
+            where = (stack.offsets[owner] + inside,)
+        decode = _decode_step(kind, stack.buffer, where, lay[0], metas[0], correct_unused_bits, stack.buffer.device)
 
-    def decode(**kw):
-        return decode_frames(stack.buffer, offsets, **common, **kw)
+    def verify_frames(status):
+        if copied is not None and bool(copied.any()):
+            raise ValueError(f"{what}: a fragment of a frame that spans fragments lies outside the extracted members")
+        _DECODERS[kind][1](status, owner, labels)
 
-    x = _finish_frames(decode, _check_status, metas, owner, rows, cols, dtype, raw_pixels, invert_pixels, check)
-    return x, metas, names
+    x = _finish_frames(decode, verify_frames, metas, owner, lay[0].rows, lay[0].cols, dtype, raw_pixels, invert_pixels, check)
+    return x, metas, [m.name for m in taken]
 
 
 ENCAP_HEAD_BYTES = 256                                       # PL_DICOM_ENCAP_HEAD: the bytes of every fragment the index brings back
@@ -1038,6 +1034,11 @@ class EncapIndex:
         return [block[a:b].view(dt).reshape(shape) for a, b, dt, shape in self._parts()]
 
 
+def _addressable(buf: torch.Tensor) -> torch.Tensor:
+    """``buf``, or a few bytes in its place when it is empty (an empty tensor has no address to hand to a kernel)"""
+    return buf if buf.numel() else torch.zeros(4, dtype=torch.uint8, device=buf.device)
+
+
 def index_encapsulated(buffer, first, end, cap: int, tcap: int, head_bytes: int = ENCAP_HEAD_BYTES, device=None,
                        block: torch.Tensor | None = None) -> EncapIndex:
     """``pl_dicom_encap_index``: the items of M encapsulated Pixel Data values lying anywhere inside ``buffer`` (uint8 array /
@@ -1050,9 +1051,7 @@ def index_encapsulated(buffer, first, end, cap: int, tcap: int, head_bytes: int 
     ``tcap``.  ``block``: a uint8 device tensor of the block's size to write into."""
     dev = on_device(device)
     buf = bytes_tensor(buffer, dev)
-    nbytes = int(buf.numel())
-    if nbytes == 0:
-        buf = torch.zeros(4, dtype=torch.uint8, device=dev)
+    nbytes, buf = int(buf.numel()), _addressable(buf)
     lo, hi = index_tensor(first, torch.int64, dev).reshape(-1), index_tensor(end, torch.int64, dev).reshape(-1)
     m = int(lo.numel())
     if int(hi.numel()) != m:
@@ -1089,10 +1088,7 @@ def copy_ranges(src, dst: torch.Tensor, src_off, length, dst_off, device=None) -
         return status[:0]
     longest = int(length.max()) if isinstance(length, torch.Tensor) else int(np.max(length, initial=0))
     src_bytes, dst_bytes = int(buf.numel()), int(dst.numel())
-    if src_bytes == 0:
-        buf = torch.zeros(4, dtype=torch.uint8, device=dev)
-    if dst_bytes == 0:
-        dst = torch.zeros(4, dtype=torch.uint8, device=dev)
+    buf, dst = _addressable(buf), _addressable(dst)
     check(_lib.load().pl_copy_ranges(buf.data_ptr(), src_bytes, dst.data_ptr(), dst_bytes, so.data_ptr(), ln.data_ptr(),
                                      do.data_ptr(), r, max(longest, 0), status.data_ptr(),
                                      torch.cuda.current_stream(dev).cuda_stream), "pl_copy_ranges")
@@ -1106,7 +1102,7 @@ def _index_members(stack, metas, lay, names, frames_span: bool) -> list:
     ``read_part10`` states them -> the heads of every member's fragments, uint8 [fragments, ENCAP_HEAD_BYTES] each."""
     base, dev = stack.offsets, stack.buffer.device
     first = base + np.asarray([m.PixelData[0] for m in metas], dtype=np.int64)
-    most = max(l[3] for l in lay)
+    most = max(l.frames for l in lay)
     cap, tcap = max(16, 2 * most), max(most, 1)
     while True:
         frags, heads, info, table = index_encapsulated(stack.buffer, first, base + stack.sizes, cap, tcap, device=dev).host()
@@ -1149,65 +1145,20 @@ def _fetch_stream_head(buffer: torch.Tensor, pieces: list, nbytes: int) -> bytes
     return (parts[0] if len(parts) == 1 else torch.cat(parts)).cpu().numpy().tobytes() if parts else b""
 
 
-def _load_zip_encapsulated(kind: str, taken, metas, lay, what: str, host, dbuf, verify: bool, check: bool, dtype, raw_pixels: bool,
-                           invert_pixels, correct_unused_bits: bool):
-    """``load_zip(encapsulated=True)`` for members that are all RLE Lossless (``kind`` "rle") or all JPEG Lossless ("jpegll"):
-    the extraction, the item walk on the device, the host's reading of the heads, the decode where the members lie."""
-    from . import zipstack
-
-    names = [f"{what}: member {m.name!r}" for m in taken]
-    _, _, ib, _, rows, cols, _, _ = lay[0]
-    if kind == "jpegll":
-        _jpegll_refusals(ib, cols)
-    stack = zipstack.run(taken, what, host, dbuf, verify=verify, check=check)
-    dev, base = stack.buffer.device, stack.offsets
-    heads = _index_members(stack, metas, lay, names, kind == "jpegll")
-    stored = int(metas[0].get("BitsStored") or ib * 8)
-    common = dict(rows=rows, cols=cols, bits_allocated=ib * 8, bits_stored=stored,
-                  pixel_representation=int(metas[0].PixelRepresentation), correct_unused_bits=correct_unused_bits, device=dev)
-    owner, seen = [], []
-    if kind == "rle":
-        windows = []
-        for k, (meta, l) in enumerate(zip(metas, lay)):
-            found = meta.PixelDataFragments
-            _rle_fragment_count(found, l[3], names[k])
-            for j, frag in enumerate(found):
-                windows.append([(int(base[k]) + o, n) for o, n in _rle_segments(heads[k][j], frag, ib, names[k])])
-                owner.append(k)
-        windows = np.asarray(windows, dtype=np.int64).reshape(-1, ib, 2)
-        seg_off, seg_len = np.ascontiguousarray(windows[:, :, 0]), np.ascontiguousarray(windows[:, :, 1])
-
-        def decode(**kw):
-            x = decode_rle_frames(stack.buffer, seg_off, seg_len, max_segment_bytes=int(seg_len.max(initial=0)), **common, **kw)
-            seen.append(x._pl_status)
-            return x
-
-        def verify_frames(x):
-            _check_rle_status(seen[-1], owner, names)
-            return x
-    else:
-        decode, copied = _zip_jpegll_decode(stack, metas, lay, names, heads, owner, seen, common)
-
-        def verify_frames(x):
-            if copied is not None and bool(copied.any()):
-                raise ValueError(f"{what}: a fragment of a frame that spans fragments lies outside the extracted members")
-            _check_jpegll_status(seen[-1], owner, names)
-            return x
-    return _finish_frames(decode, verify_frames, metas, owner, rows, cols, dtype, raw_pixels, invert_pixels, check)
-
-
-def _zip_jpegll_decode(stack, metas, lay, names, heads, owner: list, seen: list, common: dict):
-    """The JPEG Lossless half of ``_load_zip_encapsulated``: every frame's markers parsed from the heads of its fragments
+def _zip_jpegll_decode(stack, metas, lay, names, correct_unused_bits: bool):
+    """The JPEG Lossless half of ``load_zip(encapsulated=True)``: every frame's markers parsed from the heads of its fragments
     (``_jpegll_header``; leading bytes fetched from the device only when they run past the heads), a frame of one fragment
     decoded where it lies, the frames that span fragments laid end to end at 4-byte boundaries of a staging buffer by ONE
-    ``copy_ranges`` -> (decode(out=, rescale=), the copy's status or None).  ``decode_jpeg_lossless_frames`` takes one
-    buffer: with both kinds of frames it is called once per buffer, into the two parts of one native tensor."""
-    _, _, ib, _, rows, cols, _, _ = lay[0]
+    ``copy_ranges`` -> (decode(out=, rescale=) for ``_finish_frames``, the member of every frame, the copy's status or
+    None).  ``decode_jpeg_lossless_frames`` takes one buffer: with both kinds of frames it is called once per buffer, into
+    the two parts of one native tensor."""
+    rows, cols, ib = lay[0].rows, lay[0].cols, lay[0].sample_bytes
     dev, base = stack.buffer.device, stack.offsets
-    scan_off, scan_len, params, huff, staged, ranges, pos = [], [], [], [], [], [], 0
+    heads = _index_members(stack, metas, lay, names, True)
+    scans, staged, ranges, pos = [], [], [], 0
     for k, (meta, l) in enumerate(zip(metas, lay)):
         index_of = {o: j for j, (o, _) in enumerate(meta.PixelDataFragments)}
-        for frags in _jpegll_frames(meta, l[3], names[k]):
+        for frags in _jpegll_frames(meta, l.frames, names[k]):
             total = sum(n for _, n in frags)
             pieces = [(int(base[k]) + o, n) for o, n in frags]
             data = b""
@@ -1218,54 +1169,48 @@ def _zip_jpegll_decode(stack, metas, lay, names, heads, owner: list, seen: list,
             want = max(4096, 2 * len(data))                 # (the heads of many short fragments may hold more than 4 KiB)
             while True:
                 try:
-                    start, length, par, table = _jpegll_header(data, rows, cols, ib * 8, names[k], total=total)
+                    header = _jpegll_header(data, rows, cols, ib * 8, names[k], total=total)
                     break
                 except _PrefixTooShort:
                     data = _fetch_stream_head(stack.buffer, pieces, min(want, total))
                     want *= 2
+            staged.append(len(pieces) > 1)
             if len(pieces) == 1:
-                scan_off.append(pieces[0][0] + start)
+                scans.append((k, pieces[0][0], header))
             else:
+                scans.append((k, pos, header))
                 at = pos
                 for o, n in pieces:
                     ranges.append((o, n, at))
                     at += n
-                scan_off.append(pos + start)
                 pos += (total + 3) & ~3
-            staged.append(len(pieces) > 1)
-            owner.append(k)
-            scan_len.append(length)
-            params.append(par)
-            huff.append(np.frombuffer(table, dtype=np.uint8))
-    scan_off, scan_len = np.asarray(scan_off, dtype=np.int64), np.asarray(scan_len, dtype=np.int64)
-    params, huff, staged = np.asarray(params, dtype=np.int32).reshape(-1, 4), np.stack(huff), np.asarray(staged, dtype=bool)
+    tables, owner = _jpegll_tables(scans)
+    staged = np.asarray(staged, dtype=bool)
     staging = copied = None
     if ranges:
         moves = np.asarray(ranges, dtype=np.int64)
         staging = torch.empty(max(pos, 16), dtype=torch.uint8, device=dev)
         copied = copy_ranges(stack.buffer, staging, moves[:, 0], moves[:, 1], moves[:, 2], device=dev)
     groups = [(buf, np.flatnonzero(sel)) for buf, sel in ((stack.buffer, ~staged), (staging, staged)) if sel.any()]
+    if len(groups) == 1:
+        return _decode_step("jpegll", groups[0][0], tables, lay[0], metas[0], correct_unused_bits, dev), owner, copied
+    common = _decode_keywords(lay[0], metas[0], correct_unused_bits, dev)
+    bits, rep = common["bits_allocated"], common["pixel_representation"]
+    back = torch.from_numpy(np.argsort(np.concatenate([idx for _, idx in groups]))).to(dev)
 
-    def decode(**kw):
-        if len(groups) == 1:
-            x = decode_jpeg_lossless_frames(groups[0][0], scan_off, scan_len, params, huff, **common, **kw)
-        else:                                               # one call per buffer, then the frames back into their order
-            bits, rep = common["bits_allocated"], common["pixel_representation"]
-            native = torch.empty((scan_off.size, rows * cols * ib), dtype=torch.uint8, device=dev)
-            status, done = [], 0
-            for buf, idx in groups:
-                part = decode_jpeg_lossless_frames(buf, scan_off[idx], scan_len[idx], params[idx], huff[idx], rows, cols, bits,
-                                                   device=dev, native=native[done:done + idx.size])
-                status.append(part._pl_status)
-                done += idx.size
-            back = torch.from_numpy(np.argsort(np.concatenate([idx for _, idx in groups]))).to(dev)
-            cont = {(8, 0): torch.uint8, (8, 1): torch.int8, (16, 0): torch.uint16, (16, 1): torch.int16}[(bits, rep)]
-            x = _from_native(native[back], torch.cat(status)[back], cont, rows, cols, bits, common["bits_stored"], rep,
-                             common["correct_unused_bits"], kw.get("out", "container"), kw.get("rescale"), dev)
-        seen.append(x._pl_status)                            # (an integer astype hands on a tensor without it)
-        return x
+    def decode(out="container", rescale=None):              # one call per buffer, then the frames back into their order
+        native = torch.empty((len(owner), rows * cols * ib), dtype=torch.uint8, device=dev)
+        status, done = [], 0
+        for buf, idx in groups:
+            part = decode_jpeg_lossless_frames(buf, *(t[idx] for t in tables), rows, cols, bits, device=dev,
+                                               native=native[done:done + idx.size])
+            status.append(part._pl_status)
+            done += idx.size
+        x = _from_native(native[back], torch.cat(status)[back], rows, cols, bits, common["bits_stored"], rep, correct_unused_bits,
+                         out, rescale, dev)
+        return x, x._pl_status
 
-    return decode, copied
+    return decode, owner, copied
 
 
 def _astype(x: torch.Tensor, np_dt: np.dtype) -> torch.Tensor:
@@ -1309,8 +1254,7 @@ class DicomImage(_image_base()):
         frames, metas = load_frames([path], dtype=dtype, raw_pixels=raw_pixels, invert_pixels=invert_pixels,
                                     jpeg_lossless=jpeg_lossless)
         self.metadata = metas[0]
-        tdt = _layout(self.metadata)[0]
-        self._original_dtype = np.dtype(str(tdt).replace("torch.", ""))
+        self._original_dtype = np.dtype(str(_layout(self.metadata).container).replace("torch.", ""))
         arr = _to_numpy(frames)
         self.array = arr[0] if arr.shape[0] == 1 else arr      # pydicom: (rows, cols) for one frame, (frames, rows, cols) else
         self.metrics = []

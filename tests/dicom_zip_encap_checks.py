@@ -381,6 +381,7 @@ def check_scan_status(dev):
     x, _, _ = dicom.load_zip(data, device=dev, encapsulated=True, check=False)
     assert x._pl_status.cpu().tolist() == [0, 2]
     assert f"({ARCHIVE}: member 'f1.dcm', frame 1 of the stack)" in same_error(dev, data, "f1.dcm")
+    same_error(dev, data, "f1.dcm", dtype=np.int32, raw_pixels=True)
 
 
 def check_kinds_and_defaults(dev):

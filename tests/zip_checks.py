@@ -492,6 +492,14 @@ def check_load_zip_refusals(dev):
     cut = rle.native_file(frames[2:3])[:-70]
     with pytest.raises(ValueError, match="Pixel Data value .* lies outside the file"):
         dicom.load_zip(dicom_zip(native + [("cut.dcm", cut)]), device=dev)
+    # a Pixel Data element that ends inside the frame it states: load_frames's refusal in its words, an integer dtype included
+    short = rle._meta("1.2.840.10008.1.2.1") + rle.image_tags(frames[2:3]) + rle._el(0x7FE0, 0x0010, "OW", frames[2].tobytes()[:-70])
+    for kw in ({}, dict(dtype=np.int32, raw_pixels=True)):
+        with pytest.raises(ValueError, match=r"\(2030 bytes\) doesn't match the expected length \(2100 bytes\)") as want:
+            dicom.load_frames([f for _, f in native] + [short], device=dev, **kw)
+        with pytest.raises(ValueError) as got:
+            dicom.load_zip(dicom_zip(native + [("short.dcm", short)]), device=dev, **kw)
+        assert str(got.value) == str(want.value)
     # verify: a damaged pixel byte in a stored member
     data = dicom_zip(native, kinds=[zipfile.ZIP_DEFLATED, zipfile.ZIP_STORED])
     m = zipstack.read_zip(data)[1]
