@@ -411,6 +411,30 @@ def test_find_peaks_vs_oracle_random(dev):
             assert np.array_equal(p1[k], p2[k]), (trial, k)
         n_peaks += len(i1)
     assert n_peaks > 1000
+    # fixed lengths: the shortest profiles, and one below / at / above a wave (64), the one-wave-per-profile limit (128) and
+    # a workgroup (256), each with every keyword set of the cycle
+    trial = 0
+    for L in (2, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257):
+        for _ in range(6):
+            if trial % 4 == 0:
+                x = rng.integers(0, 7, L).astype(float)  # plateaus
+            else:
+                x = np.abs(rng.normal(size=L).cumsum())
+            kws = [dict(), dict(threshold=0.3, peak_separation=0.05),
+                   dict(threshold=0.5, peak_separation=0.02, peak_sort="peak_heights",
+                        required_prominence=0.1 * np.ptp(x), max_number=3),
+                   dict(search_region=(0.2, 0.8), max_number=2), dict(fwxm_height=0.3, max_number=1),
+                   dict(threshold=0.2, peak_separation=3, peak_sort="widths", max_number=4)]
+            kw = dict(kws[trial % len(kws)])
+            if trial % 4 == 0:
+                kw.pop("peak_separation", None)
+                kw.pop("max_number", None)
+            i1, p1 = o.find_peaks(x, **kw)
+            i2, p2 = ops.find_peaks_batch(T(x, dev), **kw).to_host(0)
+            assert np.array_equal(i1, i2), (L, trial, kw)
+            for k in p1:
+                assert np.array_equal(p1[k], p2[k]), (L, trial, k)
+            trial += 1
 
 
 def test_field_cax_driven_by_tile_maxima_equals_the_full_pass(dev):
