@@ -601,6 +601,47 @@ int64_t pl_dicom_jpegll_work_bytes(int64_t n_frames, int rows, int cols);
 int pl_dicom_jpegll_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_scan_off, const int64_t* d_scan_len,
                            const int32_t* d_params, const unsigned char* d_huff, int64_t n_frames, int rows, int cols,
                            int bytes_per_sample, unsigned char* d_native, int32_t* d_status, void* d_work, void* stream);
+/* JPEG 2000 lossless Pixel Data (transfer syntaxes 1.2.840.10008.1.2.4.90 and, with a reversible stream, .91: ITU-T T.800, one
+ * component, one tile and tile-part, one quality layer, the reversible 5/3 transform, no quantisation, code-block style 0) ->
+ * the same native little-endian frame buffer, for a batch of frames whose code-block segments lie anywhere inside one device
+ * buffer.  The host reads each frame's main header and its packet headers (tier 2, T.800 Annex B) and hands over
+ *   d_blocks int64 [n_blocks][PL_J2K_BLOCK_FIELDS], one row per INCLUDED code block of the whole stack: the frame; the byte
+ *   offset and the length of its segment in d_bytes (any alignment); the number of coding passes; the magnitude bit planes
+ *   (Mb - zero bit planes, Mb = guard bits + exponent - 1); the subband orientation (0 LL, 1 HL, 2 LH, 3 HH: it selects the
+ *   zero-coding contexts of Table D.1); x0, y0, width and height of the rectangle it fills in the frame's coefficient plane
+ *   (rows x cols, the subbands where the transform's levels leave them: the low band first along either axis);
+ *   d_params int32 [n_frames][4]: decomposition levels (0 .. max_levels), the precision P (1 .. 8 * bytes_per_sample), 1 for a
+ *   signed stream else 0, 0.
+ * Tier 1, one wave per block in one launch (Annexes C and D): the MQ decoder with its 47-state table and 19 contexts (reset at
+ * the block's start: UNIFORM at state 46, run length at 3, the zero-coding context without neighbours at 4, the others at 0),
+ * FF followed by a byte above 8F ends the data and 1-bits are fed beyond the segment's end; cleanup on the top bit plane, then
+ * significance propagation, magnitude refinement and cleanup per plane over stripes of four rows, contexts from the eight
+ * neighbours inside the block.  The coefficients go to the block's rectangle of an int32 plane in d_work that was zeroed
+ * before (a block that is not included has the coefficient 0).  Then the inverse 5/3 transform (Annex F.3, whole-sample
+ * symmetric extension on both axes, x[2n] = L[n] - ((H[n-1] + H[n] + 2) >> 2), x[2n+1] = H[n] + ((x[2n] + x[2n+2]) >> 1); the
+ * low band holds ceil and the high band floor of a length, a single sample passes through) in two launches per level (rows,
+ * then columns; a level whose output is one sample is left out), and one launch that adds 2^(P-1) to unsigned streams, clamps
+ * to the P-bit range and stores d_native [n_frames][rows * cols * bytes_per_sample] (signed values in two's complement).
+ *   max_levels: an upper bound of the levels in d_params (it sets the number of launches);
+ *   d_status int32 [n_frames] (zeroed here), per frame: bit 0 a descriptor of the frame is unsound -- a block whose segment
+ *   window does not lie inside [0, nbytes) or is longer than 2^28 bytes, whose rectangle is not 1 .. 64 on a side or does not
+ *   lie inside the plane, whose orientation is not 0 .. 3, whose bit planes are not 1 .. 30 or whose passes are not
+ *   3 * planes - 2 (nothing of that block is read or stored), or parameters outside the ranges above (nothing of that frame is
+ *   stored).  A row of d_blocks whose frame is not 0 .. n_frames - 1 is skipped.  Reads stay inside the aligned dwords of
+ *   d_bytes that hold a byte of the block's window, stores inside the frame's planes and its slot of d_native; a flagged frame
+ *   does not disturb the others.  Rectangles of one frame that overlap are the caller's error.  Arithmetic-coded data is not
+ *   checked: a corrupt segment decodes to other coefficients.
+ *   d_work: pl_dicom_j2k_work_bytes() bytes on a 16-byte boundary (two int32 planes a frame, of which the first is cleared; -1 for arguments
+ *   pl_dicom_j2k_decode refuses).
+ * bytes_per_sample 1 / 2 and max_levels <= PL_J2K_MAX_LEVELS (else unsupported); 1 <= n_frames <= 65535, 0 <= n_blocks < 2^31,
+ * 1 <= rows, cols <= 65535, nbytes >= 0, max_levels >= 0, non-null pointers (d_blocks may be null when n_blocks = 0), d_bytes
+ * on a 4-byte and d_work on a 16-byte boundary (else invalid argument): checked before any launch. */
+#define PL_J2K_BLOCK_FIELDS 10
+#define PL_J2K_MAX_LEVELS 16
+int64_t pl_dicom_j2k_work_bytes(int64_t n_frames, int rows, int cols);
+int pl_dicom_j2k_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_blocks, int64_t n_blocks,
+                        const int32_t* d_params, int64_t n_frames, int max_levels, int rows, int cols, int bytes_per_sample,
+                        unsigned char* d_native, int32_t* d_status, void* d_work, void* stream);
 
 /* Encapsulated Pixel Data that is already on the device (the members of a ZIP archive after pl_zip_extract): where the
  * fragments lie, and a copy that lays fragments end to end.

@@ -16,13 +16,15 @@
 // output) or 1 + 8 / BitsAllocated-bytes x (float64 output).
 #include "pl_common.h"
 
-// jpeg_lossless.hip and dicom_encap.hip are translation units of their own in the library; the CPU emulator of the tests
+// jpeg_lossless.hip, jpeg2000.hip and dicom_encap.hip are translation units of their own in the library; the CPU emulator of the tests
 // builds a fixed list of files that holds this one, so there they are compiled as parts of this file
 #ifdef PL_HIPEMU
 #define PL_JPEGLL_IN_DICOM
 #include "jpeg_lossless.hip"
 #define PL_ENCAP_IN_DICOM
 #include "dicom_encap.hip"
+#define PL_J2K_IN_DICOM
+#include "jpeg2000.hip"
 #endif
 
 namespace {

@@ -28,7 +28,14 @@ markers (``_jpegll_header``), the frames' payloads go to the device compressed a
 (``decode_jpeg_lossless_frames``: one wave per frame, one launch, nothing read back) writes the same native buffer.  Without
 the keyword they are refused as before.
 
-``load_zip(encapsulated=True)`` reads both kinds out of ZIP archives: the members are inflated on the device, where
+With ``jpeg2000=True`` the same three take lossless JPEG 2000 files (1.2.840.10008.1.2.4.90 and, with a reversible stream,
+.91: T.800, one component, one tile, one layer, the 5/3 transform, code-block style 0): the host reads every frame's main
+header and packet headers (``_j2k_codestream``: tier 2), the payloads go to the device compressed and ``pl_dicom_j2k_decode``
+(``decode_jpeg2000_frames``: one wave per code block, then the inverse transform) writes the same native buffer.  Without
+the keyword they are refused as before, and ``load_zip`` refuses them always.
+
+``load_zip(encapsulated=True)`` reads RLE Lossless and JPEG Lossless files out of ZIP archives: the members are inflated on the
+device, where
 ``pl_dicom_encap_index`` (``index_encapsulated``) walks their items and hands the host every fragment's place and first bytes, and
 ``pl_copy_ranges`` (``copy_ranges``) lays the fragments of a JPEG frame that spans several end to end.
 """
@@ -58,6 +65,8 @@ RLE_CHUNK = 1024                                             # PL_DICOM_RLE_CHUN
 _RLE_SHORT = "The amount of decoded RLE segment data doesn't match the expected amount"
 _RLE_PADDING = "The decoded RLE segment contains non-conformant padding"
 JPEG_LOSSLESS = ("1.2.840.10008.1.2.4.57", "1.2.840.10008.1.2.4.70")   # T.81 process 14: any predictor / first-order prediction
+JPEG_2000 = ("1.2.840.10008.1.2.4.90", "1.2.840.10008.1.2.4.91")       # T.800: lossless only / either; a reversible stream is decoded
+J2K_MAX_LEVELS = 16                                          # PL_J2K_MAX_LEVELS: decomposition levels the device decode walks
 JPEGLL_MAX_COLS = 8192                                       # PL_DICOM_JPEGLL_MAX_COLS: the rows the kernel buffers in LDS
 _LONG_VRS = {b"OB", b"OD", b"OF", b"OL", b"OV", b"OW", b"SQ", b"UC", b"UN", b"UR", b"UT", b"SV", b"UV"}
 
@@ -231,22 +240,24 @@ def _element(buf: memoryview, pos: int, explicit: bool, big: bool, fragments: li
     return pos + ln, (g, el), vr, start, ln
 
 
-def read_part10(source, jpeg_lossless: bool = False) -> tuple[Metadata, np.ndarray]:
+def read_part10(source, jpeg_lossless: bool = False, jpeg2000: bool = False) -> tuple[Metadata, np.ndarray]:
     """``pydicom.dcmread(source, force=True)`` as far as the image classes need it -> (metadata, the file's bytes as a uint8
     array).  ``metadata.PixelData`` (``FloatPixelData`` / ``DoubleFloatPixelData``) is the pair (offset, length) of the value
     inside those bytes -- the samples are never copied on the host.  RLE Lossless: ``PixelData`` is (offset, -1) and
     ``metadata.PixelDataFragments`` the list of (offset, length) of the fragments.  ``jpeg_lossless=True`` walks the items of
     the two JPEG Lossless syntaxes (``JPEG_LOSSLESS``) the same way; ``metadata.PixelDataOffsetTable`` is then the Basic
-    Offset Table (a list, empty or one entry per frame).  Without it they are refused like every other encapsulated syntax."""
+    Offset Table (a list, empty or one entry per frame).  Without it they are refused like every other encapsulated syntax.
+    ``jpeg2000=True`` does the same for the two JPEG 2000 syntaxes (``JPEG_2000``)."""
     data = np.frombuffer(source_bytes(source), dtype=np.uint8)
-    return _walk_part10(memoryview(data).cast("B"), jpeg_lossless=jpeg_lossless), data
+    return _walk_part10(memoryview(data).cast("B"), jpeg_lossless=jpeg_lossless, jpeg2000=jpeg2000), data
 
 
 class _PrefixTooShort(Exception):
     """the prefix of a member ends before its (7FE0,0010) element header"""
 
 
-def _walk_part10(buf: memoryview, size: int | None = None, jpeg_lossless: bool = False, encapsulated: bool = False) -> Metadata:
+def _walk_part10(buf: memoryview, size: int | None = None, jpeg_lossless: bool = False, encapsulated: bool = False,
+                 jpeg2000: bool = False) -> Metadata:
     """The element walk of ``read_part10`` over ``buf``.  ``size`` None: ``buf`` is the whole file.  Otherwise the PREFIX form
     ``load_zip`` uses: ``buf`` holds the first bytes of a file of ``size`` bytes, the walk stops at the Pixel Data element
     header -- (offset, length) of its value are validated against ``size``, not against the prefix -- and raises
@@ -256,14 +267,15 @@ def _walk_part10(buf: memoryview, size: int | None = None, jpeg_lossless: bool =
     n = len(buf)
     whole = size is None or n >= size
     try:
-        return _walk_elements(buf, n, size, whole, jpeg_lossless, encapsulated and size is not None)
+        return _walk_elements(buf, n, size, whole, jpeg_lossless, encapsulated and size is not None, jpeg2000)
     except struct.error:
         if whole:
             raise
         raise _PrefixTooShort from None
 
 
-def _walk_elements(buf: memoryview, n: int, size, whole: bool, jpeg_lossless: bool = False, items_later: bool = False) -> Metadata:
+def _walk_elements(buf: memoryview, n: int, size, whole: bool, jpeg_lossless: bool = False, items_later: bool = False,
+                   jpeg2000: bool = False) -> Metadata:
     pos = 132 if n >= 132 and bytes(buf[128:132]) == b"DICM" else 0
     values: dict = {}
     ts = IMPLICIT_LE if pos == 0 else EXPLICIT_LE          # (no preamble, force=True: pydicom assumes implicit VR little endian)
@@ -284,11 +296,12 @@ def _walk_elements(buf: memoryview, n: int, size, whole: bool, jpeg_lossless: bo
     if size is not None and ts == RLE_LOSSLESS and not items_later:
         raise NotImplementedError("RLE Lossless Pixel Data inside an archive: the segment headers lie inside the compressed part; "
                                   "extract the member and use load_frames")
-    jpegll = jpeg_lossless and size is None and ts in JPEG_LOSSLESS
-    fragments = [] if ts == RLE_LOSSLESS or jpegll else None
+    # the syntaxes whose frames may span fragments, each behind its keyword: JPEG Lossless and JPEG 2000 are walked alike
+    spanning = size is None and ((jpeg_lossless and ts in JPEG_LOSSLESS) or (jpeg2000 and ts in JPEG_2000))
+    fragments = [] if ts == RLE_LOSSLESS or spanning else None
     if items_later and (ts == RLE_LOSSLESS or ts in JPEG_LOSSLESS):
         fragments = _HEADER_ONLY
-    frame_table = [] if jpegll else None
+    frame_table = [] if spanning else None
     while pos + 8 <= n:
         pos, tag, vr, start, ln = _element(buf, pos, explicit, big, fragments, frame_table)
         if size is not None and tag == (0x7FE0, 0x0010):    # the prefix form ends here: the value is judged against the file
@@ -302,7 +315,7 @@ def _walk_elements(buf: memoryview, n: int, size, whole: bool, jpeg_lossless: bo
             raise _PrefixTooShort
         if tag == (0x7FE0, 0x0010) and ln < 0:
             values["PixelData"], values["PixelDataFragments"] = (start, -1), fragments
-            if jpegll:
+            if spanning:
                 values["PixelDataOffsetTable"] = frame_table
         if tag not in _TAGS or ln < 0:
             continue
@@ -644,10 +657,10 @@ def _jpegll_header(data, rows: int, cols: int, bits: int, name: str, total: int 
         pos += 2 + ln                                                               # APPn, COM, DQT, ...: skipped
 
 
-def _jpegll_frames(meta: Metadata, frames: int, name: str) -> list:
-    """The fragments of each frame of a JPEG Lossless file (PS3.5 section A.4, a frame may span fragments): one frame with an
-    empty Basic Offset Table owns them all, a filled table says where frames begin, and as many fragments as frames are one
-    each -> [[(offset, length), ...] per frame]; ``ValueError`` otherwise."""
+def _jpegll_frames(meta: Metadata, frames: int, name: str, codec: str = "JPEG") -> list:
+    """The fragments of each frame of a JPEG Lossless (or, ``codec``, JPEG 2000) file (PS3.5 section A.4, a frame may span
+    fragments): one frame with an empty Basic Offset Table owns them all, a filled table says where frames begin, and as many
+    fragments as frames are one each -> [[(offset, length), ...] per frame]; ``ValueError`` otherwise."""
     found, table = meta.PixelDataFragments, meta.PixelDataOffsetTable
     if table:
         if len(table) != frames or not found:
@@ -659,7 +672,7 @@ def _jpegll_frames(meta: Metadata, frames: int, name: str) -> list:
         return [list(found)]
     if len(found) == frames:
         return [[f] for f in found]
-    raise ValueError(f"{name}: {len(found)} JPEG fragments for NumberOfFrames = {frames} with an empty Basic Offset Table "
+    raise ValueError(f"{name}: {len(found)} {codec} fragments for NumberOfFrames = {frames} with an empty Basic Offset Table "
                      "(one fragment per frame, or a filled table)")
 
 
@@ -678,6 +691,360 @@ def _check_jpegll_status(status: torch.Tensor, owner, names) -> None:
         raise ValueError(f"{names[owner[k]]}, frame {k} of the stack: JPEG Lossless Pixel Data: {why}")
 
 
+def decode_jpeg2000_frames(file_bytes, blocks, params, rows: int, cols: int, bits_allocated: int, bits_stored: int | None = None,
+                           pixel_representation: int = 0, correct_unused_bits: bool = False, out: str = "container", rescale=None,
+                           device=None, native: torch.Tensor | None = None, max_levels: int | None = None) -> torch.Tensor:
+    """``pl_dicom_j2k_decode``, the JPEG 2000 counterpart of ``decode_jpeg_lossless_frames`` (T.800: one component, one tile,
+    one layer, the reversible 5/3 transform, code-block style 0): N frames whose code-block segments lie anywhere inside
+    ``file_bytes`` (uint8 array / tensor; device tensors are used in place).  ``blocks`` int64 [B, 10], one row per included
+    code block of the stack: frame, segment offset, segment length, coding passes, magnitude bit planes, subband orientation
+    (0 LL, 1 HL, 2 LH, 3 HH), then x0, y0, width, height of its rectangle in the frame's coefficient plane; ``params`` int32
+    [N, 4]: decomposition levels, precision, signed (0 / 1), 0.  One wave decodes one block (tier 1), the inverse transform
+    takes two launches per level, one launch shifts, clamps and stores.  -> device tensor [N, rows, cols] exactly as
+    ``decode_frames`` gives it for the same samples stored native (``out``, ``rescale``, ``correct_unused_bits``: the decoded
+    little-endian buffer goes through ``pl_dicom_decode``; the plain container dtype IS that buffer, returned as a view).
+    ``_pl_status`` int32 [N]: bit 0 a descriptor of the frame is unsound (a segment window outside the buffer, a rectangle
+    outside the plane, passes that are not 3 x planes - 2, parameters out of range); nothing of that block is read or stored
+    and the other frames are not disturbed.  ``max_levels``: an upper bound of the levels in ``params`` (taken from a host
+    array when absent, ``J2K_MAX_LEVELS`` for a device tensor).  ``native``: a uint8 device tensor
+    [N, rows * cols * BitsAllocated / 8] to decode into."""
+    dev = on_device(device)
+    bits, rep = int(bits_allocated), int(pixel_representation)
+    if bits not in (8, 16):
+        raise ValueError("decode_jpeg2000_frames: BitsAllocated 8 or 16")
+    if max_levels is None:
+        max_levels = J2K_MAX_LEVELS if isinstance(params, torch.Tensor) else int(np.max(np.asarray(params).reshape(-1, 4)[:, 0], initial=0))
+    if not 0 <= int(max_levels) <= J2K_MAX_LEVELS:
+        raise ValueError(f"decode_jpeg2000_frames: {max_levels} decomposition levels (0 .. {J2K_MAX_LEVELS})")
+    buf = bytes_tensor(file_bytes, dev)
+    if buf.data_ptr() % 4:                                  # (the segments are read by the aligned dword)
+        buf = buf.clone()
+    blk = index_tensor(blocks, torch.int64, dev).reshape(-1, 10)
+    par = index_tensor(params, torch.int32, dev).reshape(-1, 4)
+    n, nblk = int(par.shape[0]), int(blk.shape[0])
+    native = _native_buffer(native, n, rows * cols * (bits // 8), dev, "decode_jpeg2000_frames")
+    lib = _lib.load()
+    nwork = int(lib.pl_dicom_j2k_work_bytes(n, rows, cols))
+    if nwork < 0:
+        raise ValueError(f"decode_jpeg2000_frames: {n} frames of {rows} x {cols} (1 .. 65535 each)")
+    work = torch.empty(max(nwork, 16), dtype=torch.uint8, device=dev)
+    status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    check(lib.pl_dicom_j2k_decode(buf.data_ptr(), buf.numel(), blk.data_ptr() if nblk else None, nblk, par.data_ptr(), n,
+                                  int(max_levels), rows, cols, bits // 8, native.data_ptr(), status.data_ptr(), work.data_ptr(),
+                                  torch.cuda.current_stream(dev).cuda_stream), "pl_dicom_j2k_decode")
+    return _from_native(native, status[:n], rows, cols, bits, bits_stored, rep, correct_unused_bits, out, rescale, dev)
+
+
+_J2K = "JPEG 2000 Pixel Data: "
+_J2K_TRUNCATED = "not a lossless JPEG 2000 stream: truncated code block"
+_J2K_REFUSED = {0xFF53: "COC (coding style of a component)", 0xFF5D: "QCC (quantisation of a component)",
+                0xFF5E: "RGN (region of interest)", 0xFF5F: "POC (progression order change)", 0xFF60: "PPM (packed packet headers)",
+                0xFF61: "PPT (packed packet headers)", 0xFF50: "CAP (extended capabilities)", 0xFF59: "CPF (corresponding profile)"}
+_J2K_SKIPPED = {0xFF64, 0xFF55, 0xFF57, 0xFF58, 0xFF63}    # COM, TLM, PLM, PLT, CRG
+_J2K_MAX_PLANES = 30                                        # the device keeps a magnitude in 31 bits
+
+
+class _J2kShort(Exception):
+    """a packet header asks for a bit beyond the tile-part"""
+
+
+class _J2kBits:
+    """The bits of a packet header (T.800 B.10.1), most significant first: after a byte FF the next byte carries 7 bits."""
+
+    __slots__ = ("data", "pos", "end", "buf", "ct")
+
+    def __init__(self, data, pos: int, end: int):
+        self.data, self.pos, self.end, self.buf, self.ct = data, pos, end, 0, 0
+
+    def bit(self) -> int:
+        if self.ct == 0:
+            if self.pos >= self.end:
+                raise _J2kShort
+            self.ct = 7 if self.buf == 0xFF else 8
+            self.buf = self.data[self.pos]
+            self.pos += 1
+        self.ct -= 1
+        return (self.buf >> self.ct) & 1
+
+    def bits(self, n: int) -> int:
+        v = 0
+        for _ in range(n):
+            v = (v << 1) | self.bit()
+        return v
+
+    def align(self) -> int:
+        """the header's end: the rest of its last byte is dropped, and a last byte FF is followed by one stuffed byte"""
+        if self.buf == 0xFF:
+            if self.pos >= self.end:
+                raise _J2kShort
+            self.pos += 1
+        self.buf = self.ct = 0
+        return self.pos
+
+
+class _J2kTagTree:
+    """A tag tree over ``w`` x ``h`` leaves (T.800 B.10.2): every node keeps its value (once known) and the lower bound the
+    bits read so far have set."""
+
+    def __init__(self, w: int, h: int):
+        self.dims = [(w, h)]
+        while (w, h) != (1, 1):
+            w, h = (w + 1) // 2, (h + 1) // 2
+            self.dims.append((w, h))
+        self.value = [[1 << 30] * (a * b) for a, b in self.dims]
+        self.low = [[0] * (a * b) for a, b in self.dims]
+
+    def decode(self, bio: _J2kBits, x: int, y: int, threshold: int) -> bool:
+        """-> whether the value of leaf (x, y) is below ``threshold``, reading only the bits that settles"""
+        low = 0
+        for l in range(len(self.dims) - 1, -1, -1):
+            at = (y >> l) * self.dims[l][0] + (x >> l)
+            value = self.value[l][at]
+            low = max(low, self.low[l][at])
+            while low < threshold and low < value:
+                if bio.bit():
+                    value = self.value[l][at] = low
+                else:
+                    low += 1
+            self.low[l][at] = low
+        return value < threshold
+
+
+def _j2k_passes(bio: _J2kBits) -> int:
+    """the number of coding passes of a code block (Table B.4): codewords for 1, 2, 3 .. 5, 6 .. 36, 37 .. 164"""
+    if not bio.bit():
+        return 1
+    if not bio.bit():
+        return 2
+    v = bio.bits(2)
+    if v < 3:
+        return 3 + v
+    v = bio.bits(5)
+    return 6 + v if v < 31 else 37 + bio.bits(7)
+
+
+def _j2k_main_header(mv, n: int, rows: int, cols: int, bits: int, name: str):
+    """SOC, then the marker segments up to SOT (T.800 Annex A) -> (position of SOT, levels, precision, signed, guard bits,
+    exponents per subband, (xcb, ycb), precinct exponents per resolution or None); what the main header shows of a stream this
+    path does not decode is refused here, naming the marker or the field."""
+    def u16(at):
+        return (mv[at] << 8) | mv[at + 1]
+
+    def u32(at):
+        return (u16(at) << 16) | u16(at + 2)
+
+    if n >= 12 and bytes(mv[4:8]) == b"jP  ":
+        raise NotImplementedError(f"{name}: {_J2K}a JP2 file (box wrapper) where DICOM encapsulates the raw codestream")
+    if n < 2 or u16(0) != 0xFF4F:
+        raise ValueError(f"{name}: {_J2K}the codestream does not start with SOC (FF4F)")
+    pos, siz, cod, qcd = 2, None, None, None
+    while True:
+        if pos + 4 > n:
+            raise ValueError(f"{name}: {_J2K}the main header ends without SOT")
+        marker, ln = u16(pos), u16(pos + 2)
+        if marker >> 8 != 0xFF:
+            raise ValueError(f"{name}: {_J2K}a marker was expected at byte {pos} of the frame")
+        if ln < 2 or pos + 2 + ln > n:
+            raise ValueError(f"{name}: {_J2K}the segment of marker {marker:04X} lies outside the frame (cut off)")
+        if marker == 0xFF90:
+            break
+        at, size = pos + 4, ln - 2
+        if marker in _J2K_REFUSED:
+            raise NotImplementedError(f"{name}: {_J2K}marker {marker:04X}, {_J2K_REFUSED[marker]}, is not decoded by this path")
+        if marker == 0xFF51:
+            if size < 36 or size != 36 + 3 * u16(at + 34):
+                raise ValueError(f"{name}: {_J2K}malformed SIZ segment")
+            csiz = u16(at + 34)
+            if csiz != 1:
+                raise NotImplementedError(f"{name}: {_J2K}SIZ with Csiz = {csiz} components: single-component frames only")
+            xs, ys, xo, yo, xt, yt, xto, yto = (u32(at + 2 + 4 * k) for k in range(8))
+            if xo or yo or xto or yto:
+                raise NotImplementedError(f"{name}: {_J2K}SIZ with a non-zero image or tile origin (XOsiz, YOsiz, XTOsiz, YTOsiz)")
+            if mv[at + 37] != 1 or mv[at + 38] != 1:
+                raise NotImplementedError(f"{name}: {_J2K}SIZ with subsampling XRsiz x YRsiz = {mv[at + 37]} x {mv[at + 38]}")
+            if xt < xs or yt < ys:
+                raise NotImplementedError(f"{name}: {_J2K}SIZ with more than one tile (XTsiz x YTsiz = {xt} x {yt})")
+            if (ys, xs) != (rows, cols):
+                raise ValueError(f"{name}: {_J2K}SIZ states Ysiz x Xsiz = {ys} x {xs} where Rows x Columns = {rows} x {cols}")
+            prec, signed = (mv[at + 36] & 127) + 1, mv[at + 36] >> 7
+            if not 2 <= prec <= bits:
+                raise ValueError(f"{name}: {_J2K}SIZ precision {prec} (2 .. BitsAllocated = {bits})")
+            siz = (prec, signed)
+        elif marker == 0xFF52:
+            if size < 10:
+                raise ValueError(f"{name}: {_J2K}malformed COD segment")
+            scod, prog, layers, mct, levels, xcb, ycb, style, wavelet = (mv[at], mv[at + 1], u16(at + 2), mv[at + 4], mv[at + 5],
+                                                                         mv[at + 6] + 2, mv[at + 7] + 2, mv[at + 8], mv[at + 9])
+            if levels > 32 or size != 10 + (levels + 1 if scod & 1 else 0) or prog > 4 or scod > 7 or xcb > 10 or ycb > 10 or xcb + ycb > 12:
+                raise ValueError(f"{name}: {_J2K}malformed COD segment")
+            if scod & 6:
+                raise NotImplementedError(f"{name}: {_J2K}COD with SOP or EPH markers in the packets (Scod = {scod:#04x})")
+            if layers != 1:
+                raise NotImplementedError(f"{name}: {_J2K}COD with {layers} quality layers: one layer only")
+            if mct:
+                raise NotImplementedError(f"{name}: {_J2K}COD with a multiple-component transform")
+            if wavelet != 1:
+                raise NotImplementedError(f"{name}: {_J2K}COD selects the irreversible 9/7 transform: only the reversible 5/3 "
+                                          "transform (lossless) is decoded by this path")
+            if style:
+                raise NotImplementedError(f"{name}: {_J2K}COD with code-block style {style:#04x}: style 0 only")
+            if levels > J2K_MAX_LEVELS:
+                raise NotImplementedError(f"{name}: {_J2K}COD with {levels} decomposition levels: at most J2K_MAX_LEVELS = "
+                                          f"{J2K_MAX_LEVELS}")
+            if xcb > 6 or ycb > 6:
+                raise NotImplementedError(f"{name}: {_J2K}COD with code blocks of {1 << xcb} x {1 << ycb}: at most 64 on a side")
+            cod = (levels, xcb, ycb, [(mv[at + 10 + r] & 15, mv[at + 10 + r] >> 4) for r in range(levels + 1)] if scod & 1 else None)
+        elif marker == 0xFF5C:
+            if size < 2:
+                raise ValueError(f"{name}: {_J2K}malformed QCD segment")
+            if mv[at] & 31:
+                raise NotImplementedError(f"{name}: {_J2K}QCD with quantisation style {mv[at] & 31}: style 0 (none, reversible) only")
+            qcd = (mv[at] >> 5, [mv[at + 1 + k] >> 3 for k in range(size - 1)])
+        elif marker not in _J2K_SKIPPED:
+            raise NotImplementedError(f"{name}: {_J2K}marker {marker:04X} in the main header is not decoded by this path")
+        pos += 2 + ln
+    if siz is None or cod is None or qcd is None:
+        raise ValueError(f"{name}: {_J2K}SOT before " + ("SIZ" if siz is None else "COD" if cod is None else "QCD"))
+    if len(qcd[1]) < 3 * cod[0] + 1:
+        raise ValueError(f"{name}: {_J2K}QCD holds {len(qcd[1])} exponents where {cod[0]} levels need {3 * cod[0] + 1}")
+    return pos, cod[0], siz[0], siz[1], qcd[0], qcd[1], (cod[1], cod[2]), cod[3]
+
+
+def _j2k_codestream(data, rows: int, cols: int, bits: int, name: str):
+    """One frame's JPEG 2000 codestream (``data``: its bytes, a uint8 array) -> (levels, precision, signed, [(segment offset
+    inside ``data``, length, passes, magnitude bit planes, orientation, x0, y0, w, h)] per included code block).  The main
+    header (``_j2k_main_header``), SOT and SOD, then tier 2 (T.800 Annex B): one packet per resolution of the one tile -- the
+    zero-length bit, per subband the inclusion and zero-bit-plane tag trees, the passes, ``Lblock`` and the segment length of
+    every included block, the header byte-aligned -- and the packet's body, the segments in the same order.
+    ``NotImplementedError`` for what this path does not decode, ``ValueError`` for a malformed or truncated stream."""
+    mv = memoryview(np.ascontiguousarray(data, dtype=np.uint8))
+    n = len(mv)
+    sot, levels, prec, signed, guard, exps, (xcb, ycb), precincts = _j2k_main_header(mv, n, rows, cols, bits, name)
+
+    def u16(at):
+        return (mv[at] << 8) | mv[at + 1]
+
+    if u16(sot + 2) != 10:
+        raise ValueError(f"{name}: {_J2K}malformed SOT segment")
+    isot, psot, tpsot, tnsot = u16(sot + 4), (u16(sot + 6) << 16) | u16(sot + 8), mv[sot + 10], mv[sot + 11]
+    if isot:
+        raise NotImplementedError(f"{name}: {_J2K}SOT of tile {isot}: one tile only")
+    if tpsot or tnsot > 1:
+        raise NotImplementedError(f"{name}: {_J2K}SOT with TPsot = {tpsot}, TNsot = {tnsot}: more than one tile-part")
+    if psot:
+        end = sot + psot
+        if psot < 14 or end > n:
+            raise ValueError(f"{name}: {_J2K}SOT states a tile-part of {psot} bytes where {n - sot} are left (cut off)")
+        if end + 2 <= n and u16(end) == 0xFF90:
+            raise NotImplementedError(f"{name}: {_J2K}a second SOT: more than one tile-part")
+    else:                                                   # up to EOC (an item's pad byte may follow it)
+        end = n - 2 if n >= 2 and u16(n - 2) == 0xFFD9 else n - 3 if n >= 3 and u16(n - 3) == 0xFFD9 else n
+    pos = sot + 12
+    while True:                                             # the tile-part header
+        if pos + 2 > end:
+            raise ValueError(f"{name}: {_J2K}the tile-part header ends without SOD")
+        marker = u16(pos)
+        if marker == 0xFF93:
+            pos += 2
+            break
+        if marker in _J2K_REFUSED or marker in (0xFF52, 0xFF5C):
+            what = _J2K_REFUSED.get(marker, "COD / QCD in a tile-part header")
+            raise NotImplementedError(f"{name}: {_J2K}marker {marker:04X}, {what}, is not decoded by this path")
+        if marker not in _J2K_SKIPPED:
+            raise ValueError(f"{name}: {_J2K}marker {marker:04X} where the tile-part header or SOD was expected")
+        if pos + 4 > end or u16(pos + 2) < 2 or pos + 2 + u16(pos + 2) > end:
+            raise ValueError(f"{name}: {_J2K}the segment of marker {marker:04X} lies outside the tile-part (cut off)")
+        pos += 2 + u16(pos + 2)
+    # ---- the geometry: resolutions, subbands (the low band first along either axis), code blocks ---------------------------
+    res = [((cols + (1 << d) - 1) >> d, (rows + (1 << d) - 1) >> d) for d in range(levels, -1, -1)]
+    blocks = []
+    for r, (rw, rh) in enumerate(res):
+        ppx, ppy = precincts[r] if precincts else (15, 15)
+        if ((rw + (1 << ppx) - 1) >> ppx) > 1 or ((rh + (1 << ppy) - 1) >> ppy) > 1:
+            raise NotImplementedError(f"{name}: {_J2K}COD states precincts of {1 << ppx} x {1 << ppy} at resolution {r} of "
+                                      f"{rw} x {rh}: more than one precinct in a resolution")
+        if r and (ppx == 0 or ppy == 0):
+            raise ValueError(f"{name}: {_J2K}COD states a precinct exponent 0 above resolution 0")
+        cbw, cbh = 1 << min(xcb, ppx - (r > 0)), 1 << min(ycb, ppy - (r > 0))
+        if r == 0:
+            bands = [(0, 0, 0, rw, rh, exps[0])]
+        else:
+            lw, lh = res[r - 1]
+            bands = [(1, lw, 0, rw - lw, lh, exps[3 * r - 2]), (2, 0, lh, lw, rh - lh, exps[3 * r - 1]), (3, lw, lh, rw - lw, rh - lh, exps[3 * r])]
+        bio, found = _J2kBits(mv, pos, end), []
+        try:
+            if bio.bit():
+                for orient, bx, by, bw, bh, exponent in bands:
+                    if bw == 0 or bh == 0:
+                        continue
+                    ncx, ncy = (bw + cbw - 1) // cbw, (bh + cbh - 1) // cbh
+                    inclusion, zero_planes = _J2kTagTree(ncx, ncy), _J2kTagTree(ncx, ncy)
+                    for cy in range(ncy):
+                        for cx in range(ncx):
+                            if not inclusion.decode(bio, cx, cy, 1):
+                                continue
+                            z = 1
+                            while not zero_planes.decode(bio, cx, cy, z):
+                                z += 1
+                            passes, lblock = _j2k_passes(bio), 3
+                            while bio.bit():
+                                lblock += 1
+                            length = bio.bits(lblock + passes.bit_length() - 1)
+                            found.append((length, passes, guard + exponent - 1 - (z - 1), orient, bx + cx * cbw, by + cy * cbh,
+                                          min(cbw, bw - cx * cbw), min(cbh, bh - cy * cbh)))
+            pos = bio.align()
+        except _J2kShort:
+            raise ValueError(f"{name}: {_J2K}the packet header of resolution {r} runs out of bytes") from None
+        for length, passes, planes, *rest in found:
+            if passes != 3 * planes - 2 or planes < 1:
+                raise ValueError(f"{name}: {_J2K_TRUNCATED} ({passes} coding passes for {planes} magnitude bit planes)")
+            if planes > _J2K_MAX_PLANES:
+                raise NotImplementedError(f"{name}: {_J2K}a code block of {planes} magnitude bit planes: at most {_J2K_MAX_PLANES}")
+            if length > end - pos:
+                raise ValueError(f"{name}: {_J2K_TRUNCATED} (its segment reaches beyond the tile-part)")
+            blocks.append((pos, length, passes, planes, *rest))
+            pos += length
+    return levels, prec, signed, blocks
+
+
+def _j2k_refusals(ib: int) -> None:
+    """what a JPEG 2000 stack is refused for before any of its streams is read"""
+    if ib not in (1, 2):
+        raise NotImplementedError(f"JPEG 2000 Pixel Data with BitsAllocated {ib * 8}: 8 and 16 are decoded on the device")
+
+
+def _j2k_stage(metas, blobs, lay, names):
+    """The host side of a JPEG 2000 stack, as ``_jpegll_stage``: every frame's fragment payloads end to end at a 4-byte
+    boundary of one host buffer, its headers and packet headers parsed where they lie (``_j2k_codestream``) -> (the staging
+    buffer, (blocks, params) as ``decode_jpeg2000_frames`` takes them, the file of every frame); every refusal of a file
+    happens here, before anything is copied to the device."""
+    rows, cols, ib = lay[0].rows, lay[0].cols, lay[0].sample_bytes
+    _j2k_refusals(ib)
+    pieces, table, params, owner, pos = [], [], [], [], 0
+    for k, (m, b, l) in enumerate(zip(metas, blobs, lay)):
+        for frags in _jpegll_frames(m, l.frames, names[k], "JPEG 2000"):
+            data = b[frags[0][0]:frags[0][0] + frags[0][1]] if len(frags) == 1 else np.concatenate([b[o:o + n] for o, n in frags])
+            levels, prec, signed, blocks = _j2k_codestream(data, rows, cols, ib * 8, names[k])
+            table += [(len(owner), pos + at, *rest) for at, *rest in blocks]
+            params.append((levels, prec, signed, 0))
+            owner.append(k)
+            pieces.append((pos, data))
+            pos += (len(data) + 3) & ~3
+    host = np.zeros(pos, dtype=np.uint8)
+    for at, data in pieces:
+        host[at:at + len(data)] = data
+    return host, (np.asarray(table, dtype=np.int64).reshape(-1, 10), np.asarray(params, dtype=np.int32).reshape(-1, 4)), owner
+
+
+def _check_j2k_status(status: torch.Tensor, owner, names) -> None:
+    """``ValueError`` naming the file and the frame for the first flagged frame of ``decode_jpeg2000_frames`` (one
+    transfer)."""
+    bad = np.flatnonzero(status.cpu().numpy())
+    if bad.size:
+        k = int(bad[0])
+        raise ValueError(f"{names[owner[k]]}, frame {k} of the stack: {_J2K}a code-block descriptor or a parameter is unsound")
+
+
 def _check_native_status(status: torch.Tensor, owner=None, names=None) -> None:
     if bool(status.any()):
         raise ValueError("The length of the pixel data in the dataset doesn't match the expected length; the dataset may be "
@@ -693,22 +1060,24 @@ def _check_status(frames: torch.Tensor) -> torch.Tensor:
 
 _MIXED_JPEGLL = "load_frames: JPEG Lossless files are mixed with native or RLE Lossless files; load the kinds separately"
 _MIXED_RLE = "load_frames: native and RLE Lossless files are mixed; load the two kinds separately"
+_MIXED_J2K = "load_frames: JPEG 2000 files are mixed with native, RLE Lossless or JPEG Lossless files; load the kinds separately"
 _DECODERS = {"native": (decode_frames, _check_native_status), "rle": (decode_rle_frames, _check_rle_status),
-             "jpegll": (decode_jpeg_lossless_frames, _check_jpegll_status)}
+             "jpegll": (decode_jpeg_lossless_frames, _check_jpegll_status), "j2k": (decode_jpeg2000_frames, _check_j2k_status)}
 
 
 def _frame_plan(metas, who: str, noun: str):
     """What ``load_frames`` (``noun``: files) and ``load_zip`` (members) settle as soon as the headers are parsed, before a
-    fragment is looked at: one pixel format and frame size, one kind -> (kind "native" | "rle" | "jpegll", the layouts, and
+    fragment is looked at: one pixel format and frame size, one kind -> (kind "native" | "rle" | "jpegll" | "j2k", the layouts, and
     for native data the file of every frame and the frame's offset inside that file)."""
     lay = [_layout(m) for m in metas]
     first = lay[0]
     for l in lay[1:]:
         if l.format != first.format:
             raise ValueError(f"{who}: the {noun} differ in pixel format or frame size (the reference's stacks refuse that too)")
-    kinds = {"native" if m.PixelData[1] >= 0 else "rle" if m.TransferSyntaxUID == RLE_LOSSLESS else "jpegll" for m in metas}
+    kinds = {"native" if m.PixelData[1] >= 0 else "rle" if m.TransferSyntaxUID == RLE_LOSSLESS else
+             "j2k" if m.TransferSyntaxUID in JPEG_2000 else "jpegll" for m in metas}
     if len(kinds) > 1:
-        raise ValueError(_MIXED_JPEGLL if "jpegll" in kinds else _MIXED_RLE)
+        raise ValueError(_MIXED_J2K if "j2k" in kinds else _MIXED_JPEGLL if "jpegll" in kinds else _MIXED_RLE)
     owner, inside = [], []
     if kinds == {"native"}:
         frame_bytes = first.rows * first.cols * first.sample_bytes
@@ -759,7 +1128,7 @@ def _decode_keywords(l: _Layout, meta: Metadata, correct_unused_bits: bool, devi
 def _decode_step(kind: str, buffer, where: tuple, l: _Layout, meta: Metadata, correct_unused_bits: bool, device):
     """-> decode(out=..., rescale=...) = (frames, status) for ``_finish_frames``: the decode of ``kind`` over ``buffer``,
     ``where`` being the arrays that place the frames in it (frame offsets | seg_off, seg_len | scan_off, scan_len, params,
-    huff)."""
+    huff | blocks, params)."""
     common = _decode_keywords(l, meta, correct_unused_bits, device)
     if kind == "native":
         common["big_endian"] = l.big_endian
@@ -774,9 +1143,11 @@ def _decode_step(kind: str, buffer, where: tuple, l: _Layout, meta: Metadata, co
 
 
 def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bool | None = None,
-                correct_unused_bits: bool = False, device=None, check: bool = True, jpeg_lossless: bool = False):
+                correct_unused_bits: bool = False, device=None, check: bool = True, jpeg_lossless: bool = False,
+                jpeg2000: bool = False):
     """The batched loader: Part-10 files (paths, bytes or file objects; every file may hold several frames) of ONE pixel
-    format, frame size and kind (all native or all RLE Lossless) -> (device tensor [N, H, W], list of per-file metadata).  Per
+    format, frame size and kind (all native or all RLE Lossless; with the keywords below all JPEG Lossless or all JPEG 2000) ->
+    (device tensor [N, H, W], list of per-file metadata).  Per
     file exactly what ``DicomImage.__init__`` does (image.py:1431-1444): ``pixel_array`` [``.astype(dtype)``] then
     ``_rescale_dicom_values``;
     files with both rescale tags take the fused float64 form of the kernel when every file carries the SAME slope and
@@ -786,18 +1157,29 @@ def load_frames(sources, dtype=None, raw_pixels: bool = False, invert_pixels: bo
     SamplesPerPixel 1, BitsAllocated 8 or 16), decoded by ``decode_jpeg_lossless_frames`` with a wave per frame.  Their files
     may differ in predictor, point transform, restart interval and Huffman table; a frame may span fragments (its payloads
     are laid end to end on the host).  ``check=True`` reads the decode's status once and raises ``ValueError`` naming the
-    file and the frame."""
+    file and the frame.
+
+    ``jpeg2000=True`` accepts a fourth kind: files of the JPEG 2000 syntaxes (``JPEG_2000``) whose streams are lossless --
+    SamplesPerPixel 1, BitsAllocated 8 or 16, a raw codestream of one component, one tile and tile-part, one quality layer,
+    the reversible 5/3 transform with up to ``J2K_MAX_LEVELS`` levels, code blocks of at most 64 x 64 in style 0, one
+    precinct per resolution.  The host reads the headers and the packet headers (``_j2k_codestream``), the device decodes
+    the code blocks with a wave each and runs the inverse transform (``decode_jpeg2000_frames``).  Everything else of
+    JPEG 2000 is refused naming the file and the marker or field (``NotImplementedError``), a malformed or truncated stream
+    is a ``ValueError``, both before anything is copied to the device.  Both keywords may be given; the kinds do not mix
+    in one call."""
     sources = list(sources)
     metas, blobs = [], []
     for s in sources:
-        m, b = read_part10(s, jpeg_lossless=jpeg_lossless)
+        m, b = read_part10(s, jpeg_lossless=jpeg_lossless, jpeg2000=jpeg2000)
         metas.append(m)
         blobs.append(b)
     names = [f"file {k}" + (f" ({s})" if isinstance(s, (str, Path)) else "") for k, s in enumerate(sources)]
     kind, lay, owner, inside = _frame_plan(metas, "load_frames", "files")
     if kind == "jpegll":
         host, where, owner = _jpegll_stage(metas, blobs, lay, names)
-    else:                                                    # one host buffer, every file at a 4-byte boundary
+    elif kind == "j2k":
+        host, where, owner = _j2k_stage(metas, blobs, lay, names)
+    else:                                                   # one host buffer, every file at a 4-byte boundary
         starts = np.cumsum([0] + [(len(b) + 3) & ~3 for b in blobs])
         if kind == "rle":
             *where, owner = _rle_windows(metas, lay, names, starts,
@@ -1247,12 +1629,12 @@ class DicomImage(_image_base()):
     class-API image; ``metadata`` answers the tags the reference's properties read."""
 
     def __init__(self, path, *, dtype=None, dpi: float = None, sid: float = None, sad: float = 1000, raw_pixels: bool = False,
-                 invert_pixels: bool | None = None, jpeg_lossless: bool = False):
+                 invert_pixels: bool | None = None, jpeg_lossless: bool = False, jpeg2000: bool = False):
         self.path = path
         self._sid, self._dpi, self._sad = sid, dpi, sad
         self._raw_pixels, self._invert_pixels = raw_pixels, invert_pixels
         frames, metas = load_frames([path], dtype=dtype, raw_pixels=raw_pixels, invert_pixels=invert_pixels,
-                                    jpeg_lossless=jpeg_lossless)
+                                    jpeg_lossless=jpeg_lossless, jpeg2000=jpeg2000)
         self.metadata = metas[0]
         self._original_dtype = np.dtype(str(_layout(self.metadata).container).replace("torch.", ""))
         arr = _to_numpy(frames)
