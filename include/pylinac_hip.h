@@ -642,6 +642,43 @@ int64_t pl_dicom_j2k_work_bytes(int64_t n_frames, int rows, int cols);
 int pl_dicom_j2k_decode(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_blocks, int64_t n_blocks,
                         const int32_t* d_params, int64_t n_frames, int max_levels, int rows, int cols, int bytes_per_sample,
                         unsigned char* d_native, int32_t* d_status, void* d_work, void* stream);
+/* Tier 2 on the device: pl_dicom_j2k_plan reads the packet headers of n_frames codestreams where they lie in d_bytes (one
+ * packet per resolution; the zero-length bit, per subband the inclusion and the zero-bit-plane tag tree, the passes of Table
+ * B.4, Lblock and the segment length of every included block, the header byte-aligned, then the body) and writes the rows of
+ * d_blocks that pl_dicom_j2k_decode takes -- one wave per frame, nothing read back.  The host reads the main header, SOT and
+ * the tile-part header and hands over, per frame,
+ *   d_plan int64 [n_frames][PL_J2K_PLAN_FIELDS]: 0 the byte of d_bytes the codestream starts at; 1 its length; 2 the offset of
+ *   the first packet inside it (the byte after SOD); 3 the tile-part's end inside it, or 0 for Psot = 0: the tile-part then
+ *   ends in front of an EOC that closes the stream, or that one pad byte follows, else at the stream's end; 4 the coding
+ *   parameters: decomposition levels | xcb << 8 | ycb << 16 | guard bits << 24 | (1 if the precincts are stated) << 32,
+ *   xcb and ycb being the exponents of the code-block size (2 .. 6); 5 the first row of d_blocks that belongs to the frame;
+ *   6 the rows it owns: one for EVERY code block of the geometry, included or not; 7 zero;
+ *   d_tables uint8 [n_frames][PL_J2K_PLAN_TABLE]: bytes 0 .. 48 the exponent of each subband in QCD's order (LL, then HL, LH,
+ *   HH per resolution; at most 31), bytes 49 .. 65 per resolution the precinct exponents PPx | PPy << 4 (read only when the
+ *   precincts are stated), the rest unused.
+ * rows and cols are the stack's frame size.  The rows of the included blocks are filled from the front of the frame's range
+ * in the order the headers name them (the frame is the index in this call); the other rows of the range receive frame = -1,
+ * which pl_dicom_j2k_decode skips.
+ *   d_info int32 [n_frames][4]: status, the number of included blocks, two details.  Status 1: the plan row is unsound (a
+ *   window outside d_bytes or longer than 2^27 bytes, offsets outside the stream, parameters out of range, more than one
+ *   precinct in a resolution, a precinct exponent 0 above resolution 0, a tag tree of more than max_nodes nodes, rows outside
+ *   d_blocks or not as many as the geometry has code blocks) -- nothing but the status is written; 2: the packet header of
+ *   resolution `detail 0` runs out of bytes; 4: a block of `detail 0` passes and `detail 1` bit planes (not 3 x planes - 2, or
+ *   planes < 1); 8: a block of `detail 0` bit planes (more than 30); 16: a segment reaches beyond the tile-part.  The first
+ *   fault is reported: a packet's whole header first, then its blocks in order, each for passes, planes, length.  Every row
+ *   of a flagged frame has frame = -1 and its count is 0; the other frames are not disturbed.
+ *   d_work: pl_dicom_j2k_plan_work_bytes(n_frames, max_nodes) bytes on a 16-byte boundary (the two tag trees of a frame, a
+ *   node two int32 values; -1 for arguments the call refuses); max_nodes: the nodes of the largest tag tree of any frame.
+ * Reads stay inside [stream start, tile-part end), stores inside the frame's rows, its row of d_info and its slice of d_work.
+ * 1 <= n_frames <= 65535, 0 <= n_blocks < 2^31, 1 <= rows, cols <= 65535, nbytes >= 0, 1 <= max_nodes <= 2^24, non-null
+ * pointers (d_blocks may be null when n_blocks = 0), d_work on a 16-byte boundary (else invalid argument): checked before the
+ * launch. */
+#define PL_J2K_PLAN_FIELDS 8
+#define PL_J2K_PLAN_TABLE 72
+int64_t pl_dicom_j2k_plan_work_bytes(int64_t n_frames, int64_t max_nodes);
+int pl_dicom_j2k_plan(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_plan, const unsigned char* d_tables,
+                      int64_t n_frames, int rows, int cols, int64_t* d_blocks, int64_t n_blocks, int32_t* d_info, void* d_work,
+                      int64_t max_nodes, void* stream);
 
 /* Encapsulated Pixel Data that is already on the device (the members of a ZIP archive after pl_zip_extract): where the
  * fragments lie, and a copy that lays fragments end to end.

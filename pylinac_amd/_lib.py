@@ -178,6 +178,8 @@ SIGNATURES = {
     "pl_dicom_jpegll_decode": ([_p, _l, _p, _p, _p, _p, _l, _i, _i, _i, _p, _p, _p, _p], C.c_int),
     "pl_dicom_j2k_work_bytes": ([_l, _i, _i], C.c_int64),
     "pl_dicom_j2k_decode": ([_p, _l, _p, _l, _p, _l, _i, _i, _i, _i, _p, _p, _p, _p], C.c_int),
+    "pl_dicom_j2k_plan_work_bytes": ([_l, _l], C.c_int64),
+    "pl_dicom_j2k_plan": ([_p, _l, _p, _p, _l, _i, _i, _p, _l, _p, _p, _l, _p], C.c_int),
     # encapsulated Pixel Data already on the device: the item walk and the copy that joins fragments (csrc/dicom_encap.hip)
     "pl_dicom_encap_index_bytes": ([_l, _i, _i, _i], C.c_int64),
     "pl_dicom_encap_index": ([_p, _l, _p, _p, _l, _i, _i, _i, _p, _p], C.c_int),

@@ -1,10 +1,27 @@
 // JPEG 2000 lossless Pixel Data (transfer syntaxes 1.2.840.10008.1.2.4.90 and .91 with a reversible stream: ITU-T T.800, one
 // component, one tile, one quality layer, the 5/3 transform, code-block style 0) -> the native little-endian frame buffer
-// pl_dicom_decode reads, next to jpeg_lossless.hip.  The host parses each frame's main header and its packet headers (tier 2,
-// T.800 Annex B) while the file is still host bytes; the device sees one descriptor per included code block of the whole
+// pl_dicom_decode reads, next to jpeg_lossless.hip.  The host parses each frame's main header; the packet headers (tier 2,
+// T.800 Annex B) are parsed on the host while the file is still host bytes (dicom.load_frames) or here, by j2k_tier2_kernel,
+// where the stream lies on the device (dicom.load_zip).  Either way tier 1 sees one descriptor per code block of the whole
 // stack (PL_J2K_BLOCK_FIELDS int64 values: frame, segment offset and length, coding passes, magnitude bit planes, subband
-// orientation, the rectangle it fills in the frame's coefficient plane) and four parameters per frame (decomposition levels,
-// precision, signed, 0).
+// orientation, the rectangle it fills in the frame's coefficient plane; a frame outside 0 .. n_frames - 1 marks a row that
+// is not used) and four parameters per frame (decomposition levels, precision, signed, 0).
+//
+// j2k_tier2_kernel: ONE wave per frame, one launch for the stack, nothing read back (pl_dicom_j2k_plan).
+//   input    one int64 row and one byte table per frame say what the host read of the headers (include/pylinac_hip.h);
+//            kJ2kHdrWin bytes of the stream at a time go to LDS, a dword per lane, and the reader takes a byte from LDS
+//            (readfirstlane): after a byte FF the next one carries 7 bits.  Nothing outside [stream start, tile-part end) is read.
+//   packets  dicom.py's _j2k_codestream restated: per resolution the zero-length bit, per non-empty subband (LL | HL, LH, HH)
+//            the inclusion and the zero-bit-plane tag tree, the passes (Table B.4), Lblock from 3, the length of
+//            Lblock + floor(log2 passes) bits, the header byte-aligned (one stuffed byte after a final FF), then the body.
+//   trees    a node is (value, lower bound), two int32 in the frame's slice of d_work, root first; ONE path for every tree
+//            size.  The lanes reset a subband's trees together, a workgroup fence follows; on the chain every lane stores
+//            the same pair and loads back what it stored itself (ordinary vector loads: the pointer is neither const nor
+//            __restrict__).
+//   output   the frame owns one row of d_blocks for every code block of its geometry.  An included block's row is written a
+//            field per lane while the header is read; at the header's end the packet's rows are read back, checked in the
+//            host's order (passes, planes, length) and given their offsets.  The rows left over receive frame = -1, which
+//            tier 1 skips; d_info: status, count, two details (the first fault; a flagged frame has no rows).
 //
 // j2k_tier1_kernel: ONE wave per code block, one launch for the stack, nothing read back.
 //   input    kJ2kWin bytes of the segment at a time go to LDS by the dword (aligned global dwords, funnel-shifted by the
@@ -401,7 +418,281 @@ j2k_store_kernel(const int32_t* __restrict__ planes, const int32_t* __restrict__
   else out[2 * i] = (unsigned char)v, out[2 * i + 1] = (unsigned char)((unsigned)v >> 8);
 }
 
+// ---- tier 2: the packet headers --------------------------------------------------------------------------------------------
+constexpr int kJ2kPlanF = PL_J2K_PLAN_FIELDS, kJ2kPlanT = PL_J2K_PLAN_TABLE;
+constexpr int kJ2kHdrWin = 256;                             // bytes of the stream staged at a time (a dword per lane)
+constexpr int64_t kJ2kMaxStream = 1 << 27;                  // bytes of a frame's window: a tag-tree value stays below kJ2kOpen
+constexpr int kJ2kOpen = 1 << 30;                           // the value of a tag-tree node no 1-bit has settled yet
+constexpr int64_t kJ2kLong = (int64_t)1 << 40;              // a segment length is followed exactly up to here
+
+// the bits of a packet header (B.10.1), most significant first: after a byte FF the next byte carries 7 bits
+struct __attribute__((aligned(8))) J2kNode {                 // a tag-tree node: its value (kJ2kOpen until known), the lower bound read so far
+  int value, low;
+};
+
+struct J2kBits {
+  int64_t pos, end, base;                                   // base: the byte the staged window begins with
+  unsigned buf;
+  int ct;
+  bool dry;                                                 // a bit beyond `end` was asked for (it reads as 0)
+};
+
+#define PL_J2K_HDR bytes, s_hdr, lane
+
+__device__ __forceinline__ unsigned j2k_hdr_bit(J2kBits& b, const unsigned char* __restrict__ bytes, unsigned* s_hdr, int lane) {
+  if (b.ct == 0) {
+    if (b.pos >= b.end) {
+      b.dry = true;
+      return 0u;
+    }
+    if (b.pos >= b.base + kJ2kHdrWin) {                     // (pos only ever grows)
+      b.base = b.pos;
+      __syncthreads();
+      unsigned v = 0;
+      for (int k = 0; k < 4; ++k) {
+        const int64_t at = b.base + 4 * lane + k;
+        if (at < b.end) v |= (unsigned)bytes[at] << (8 * k);
+      }
+      s_hdr[lane] = v;
+      __syncthreads();
+    }
+    const int q = (int)(b.pos - b.base);
+    b.ct = b.buf == 0xffu ? 7 : 8;
+    b.buf = (__builtin_amdgcn_readfirstlane(s_hdr[q >> 2]) >> (8 * (q & 3))) & 0xffu;
+    ++b.pos;
+  }
+  --b.ct;
+  return (b.buf >> b.ct) & 1u;
+}
+
+__device__ __forceinline__ int64_t j2k_hdr_bits(J2kBits& b, int n, const unsigned char* __restrict__ bytes, unsigned* s_hdr, int lane) {
+  int64_t v = 0;
+  for (int i = 0; i < n && !b.dry; ++i) {
+    const int64_t bit = j2k_hdr_bit(b, PL_J2K_HDR);
+    v = v >= kJ2kLong ? v : (v << 1) | bit;                 // (a length beyond 2^40 reaches beyond every tile-part)
+  }
+  return v;
+}
+
+// The nodes of the tag tree over w x h leaves (B.10.2) lie root first: a level's nodes follow those of the level above.
+__device__ __forceinline__ int j2k_tree_levels(int w, int h) {
+  int n = 1;
+  while (((w + (1 << (n - 1)) - 1) >> (n - 1)) > 1 || ((h + (1 << (n - 1)) - 1) >> (n - 1)) > 1) ++n;
+  return n;
+}
+
+__device__ __forceinline__ int64_t j2k_tree_nodes(int w, int h) {
+  int64_t n = 0;
+  for (int l = j2k_tree_levels(w, h) - 1; l >= 0; --l) n += (int64_t)((w + (1 << l) - 1) >> l) * ((h + (1 << l) - 1) >> l);
+  return n;
+}
+
+// whether the value of leaf (x, y) is below `threshold`, reading only the bits that settles.  A node is (value, lower bound);
+// every lane stores the same pair and loads back what it stored itself.
+__device__ __forceinline__ bool j2k_tag(J2kNode* tree, int w, int h, int levels, int x, int y, int threshold, J2kBits& b,
+                                        const unsigned char* __restrict__ bytes, unsigned* s_hdr, int lane) {
+  int low = 0, value = kJ2kOpen, off = 0;
+  for (int l = levels - 1; l >= 0; --l) {
+    const int wl = (w + (1 << l) - 1) >> l, hl = (h + (1 << l) - 1) >> l;
+    const int at = off + (y >> l) * wl + (x >> l);
+    const J2kNode node = tree[at];
+    value = __builtin_amdgcn_readfirstlane(node.value);
+    const int known = __builtin_amdgcn_readfirstlane(node.low);
+    low = low > known ? low : known;
+    while (low < threshold && low < value && !b.dry) {
+      if (j2k_hdr_bit(b, PL_J2K_HDR)) value = low;
+      else ++low;
+    }
+    tree[at] = J2kNode{value, low};
+    off += wl * hl;
+  }
+  return value < threshold;
+}
+
+// the number of coding passes of a code block (Table B.4): codewords for 1, 2, 3 .. 5, 6 .. 36, 37 .. 164
+__device__ __forceinline__ int j2k_hdr_passes(J2kBits& b, const unsigned char* __restrict__ bytes, unsigned* s_hdr, int lane) {
+  if (!j2k_hdr_bit(b, PL_J2K_HDR)) return 1;
+  if (!j2k_hdr_bit(b, PL_J2K_HDR)) return 2;
+  int v = (int)j2k_hdr_bits(b, 2, PL_J2K_HDR);
+  if (v < 3) return 3 + v;
+  v = (int)j2k_hdr_bits(b, 5, PL_J2K_HDR);
+  return v < 31 ? 6 + v : 37 + (int)j2k_hdr_bits(b, 7, PL_J2K_HDR);
+}
+
+// what the plan states of resolution r: the code-block size, or false for more than one precinct / an exponent 0 above r = 0
+__device__ __forceinline__ bool j2k_res_blocks(const unsigned char* __restrict__ table, bool stated, int r, int rw, int rh, int xcb, int ycb,
+                                               int& cbw, int& cbh) {
+  const int ppx = stated ? table[49 + r] & 15 : 15, ppy = stated ? table[49 + r] >> 4 : 15;
+  if (((rw + (1 << ppx) - 1) >> ppx) > 1 || ((rh + (1 << ppy) - 1) >> ppy) > 1) return false;
+  if (r && (ppx == 0 || ppy == 0)) return false;
+  const int px = ppx - (r > 0), py = ppy - (r > 0);
+  cbw = 1 << (xcb < px ? xcb : px), cbh = 1 << (ycb < py ? ycb : py);
+  return true;
+}
+
+// band b (0 .. 2; at r = 0 only 0) of resolution r -> orientation, origin and size in the coefficient plane
+__device__ __forceinline__ void j2k_band(int r, int k, int rw, int rh, int lw, int lh, int& orient, int& bx, int& by, int& bw, int& bh) {
+  if (r == 0) orient = 0, bx = 0, by = 0, bw = rw, bh = rh;
+  else if (k == 0) orient = 1, bx = lw, by = 0, bw = rw - lw, bh = lh;
+  else if (k == 1) orient = 2, bx = 0, by = lh, bw = lw, bh = rh - lh;
+  else orient = 3, bx = lw, by = lh, bw = rw - lw, bh = rh - lh;
+}
+
+// ONE wave per frame, a wave-uniform chain as tier 1: the frame's packet headers (Annex B: one packet per resolution of the one
+// tile, one precinct, one layer) -> its rows of d_blocks and its row of d_info.  `work`: two trees of max_nodes (value, lower
+// bound) pairs per frame, written and read back inside this launch (hence no __restrict__ and no const on it or on `blocks`).
+__global__ void __launch_bounds__(PL_WAVE)
+j2k_tier2_kernel(const unsigned char* __restrict__ bytes, int64_t nbytes, const int64_t* __restrict__ plan,
+                 const unsigned char* __restrict__ tables, int rows, int cols, int64_t* blocks, int64_t n_blocks,
+                 int32_t* __restrict__ info, J2kNode* work, int64_t max_nodes) {
+  __shared__ unsigned s_hdr[kJ2kHdrWin / 4];
+  const int lane = threadIdx.x;
+  const int64_t f = blockIdx.x;
+  const int64_t* p = plan + f * kJ2kPlanF;
+  const unsigned char* table = tables + f * kJ2kPlanT;
+  const int64_t start = p[0], len = p[1], first = p[2], stated_end = p[3], coding = p[4], row0 = p[5], nrows = p[6];
+  const int levels = (int)(coding & 255), xcb = (int)((coding >> 8) & 255), ycb = (int)((coding >> 16) & 255);
+  const int guard = (int)((coding >> 24) & 255);
+  const bool stated = (coding >> 32) & 1;
+  int32_t* out = info + f * 4;
+  // ---- the plan row (differences of lengths, never sums of an offset and a length) ------------------------------------------
+  bool bad = start < 0 || len < 0 || start > nbytes || len > nbytes - start || len > kJ2kMaxStream;
+  bad = bad || first < 0 || first > len || stated_end < 0 || stated_end > len || (stated_end && first > stated_end);
+  bad = bad || (coding >> 33) != 0 || levels > PL_J2K_MAX_LEVELS || xcb < 2 || ycb < 2 || xcb > 6 || ycb > 6 || guard > 7;
+  bad = bad || row0 < 0 || nrows < 0 || row0 > n_blocks || nrows > n_blocks - row0 || p[7] != 0;
+  int64_t count = 0;
+  for (int r = 0; !bad && r <= levels; ++r) {                // every code block of the geometry has a row
+    const int d = levels - r, rw = (cols + (1 << d) - 1) >> d, rh = (rows + (1 << d) - 1) >> d;
+    const int lw = (cols + (2 << d) - 1) >> (d + 1), lh = (rows + (2 << d) - 1) >> (d + 1);
+    int cbw, cbh;
+    bad = !j2k_res_blocks(table, stated, r, rw, rh, xcb, ycb, cbw, cbh);
+    for (int k = 0; !bad && k < (r ? 3 : 1); ++k) {
+      int orient, bx, by, bw, bh;
+      j2k_band(r, k, rw, rh, lw, lh, orient, bx, by, bw, bh);
+      if (bw == 0 || bh == 0) continue;
+      const int ncx = (bw + cbw - 1) / cbw, ncy = (bh + cbh - 1) / cbh;
+      bad = table[r ? 3 * r - 3 + orient : 0] > 31 || j2k_tree_nodes(ncx, ncy) > max_nodes;
+      count += (int64_t)ncx * ncy;
+    }
+  }
+  bad = bad || count != nrows;
+  int64_t end = start + (stated_end ? stated_end : len);
+  if (!bad && !stated_end) {                                 // Psot = 0: up to EOC, which an item's pad byte may follow
+    const unsigned b1 = len >= 1 ? bytes[start + len - 1] : 0u, b2 = len >= 2 ? bytes[start + len - 2] : 0u;
+    const unsigned b3 = len >= 3 ? bytes[start + len - 3] : 0u;
+    if (len >= 2 && b2 == 0xffu && b1 == 0xd9u) end -= 2;
+    else if (len >= 3 && b3 == 0xffu && b2 == 0xd9u) end -= 3;
+    end = __builtin_amdgcn_readfirstlane((int)(end - start)) + start;
+    bad = start + first > end;
+  }
+  if (bad) {                                                 // nothing but the status is written
+    if (lane == 0) out[0] = 1, out[1] = 0, out[2] = 0, out[3] = 0;
+    return;
+  }
+  // ---- the packets ----------------------------------------------------------------------------------------------------------
+  int64_t* mine = blocks + row0 * kJ2kF;
+  J2kNode* inclusion = work + f * 2 * max_nodes;
+  J2kNode* zero_planes = inclusion + max_nodes;
+  J2kBits b;
+  b.pos = start + first, b.end = end, b.base = b.pos - kJ2kHdrWin, b.dry = false;
+  int status = 0, detail0 = 0, detail1 = 0;
+  int64_t done = 0;                                          // rows filled by the packets before this one
+  for (int r = 0; !status && r <= levels; ++r) {
+    const int d = levels - r, rw = (cols + (1 << d) - 1) >> d, rh = (rows + (1 << d) - 1) >> d;
+    const int lw = (cols + (2 << d) - 1) >> (d + 1), lh = (rows + (2 << d) - 1) >> (d + 1);
+    int cbw = 0, cbh = 0;
+    j2k_res_blocks(table, stated, r, rw, rh, xcb, ycb, cbw, cbh);
+    b.buf = 0, b.ct = 0;
+    int64_t found = done;
+    if (j2k_hdr_bit(b, PL_J2K_HDR)) {                        // (0: an empty packet)
+      for (int k = 0; !b.dry && k < (r ? 3 : 1); ++k) {
+        int orient, bx, by, bw, bh;
+        j2k_band(r, k, rw, rh, lw, lh, orient, bx, by, bw, bh);
+        if (bw == 0 || bh == 0) continue;
+        const int exponent = table[r ? 3 * r - 3 + orient : 0];
+        const int ncx = (bw + cbw - 1) / cbw, ncy = (bh + cbh - 1) / cbh;
+        const int tl = j2k_tree_levels(ncx, ncy);
+        const int nodes = (int)j2k_tree_nodes(ncx, ncy);
+        __syncthreads();
+        for (int i = lane; i < nodes; i += PL_WAVE) inclusion[i] = J2kNode{kJ2kOpen, 0}, zero_planes[i] = J2kNode{kJ2kOpen, 0};
+        __syncthreads();
+        for (int cy = 0; !b.dry && cy < ncy; ++cy) {
+          for (int cx = 0; !b.dry && cx < ncx; ++cx) {
+            if (!j2k_tag(inclusion, ncx, ncy, tl, cx, cy, 1, b, PL_J2K_HDR)) continue;
+            int z = 1;
+            while (!b.dry && !j2k_tag(zero_planes, ncx, ncy, tl, cx, cy, z, b, PL_J2K_HDR)) ++z;
+            const int passes = j2k_hdr_passes(b, PL_J2K_HDR);
+            int lblock = 3;
+            while (j2k_hdr_bit(b, PL_J2K_HDR)) ++lblock;
+            for (int v = passes; v > 1; v >>= 1) ++lblock;    // + floor(log2 passes) bits
+            const int64_t length = j2k_hdr_bits(b, lblock, PL_J2K_HDR);
+            if (b.dry) break;
+            const int x0 = bx + cx * cbw, y0 = by + cy * cbh;
+            const int w = cbw < bw - cx * cbw ? cbw : bw - cx * cbw, h = cbh < bh - cy * cbh ? cbh : bh - cy * cbh;
+            // the row, a field per lane (the offset follows once the header's end is known)
+            const int64_t v = lane == 0 ? f : lane == 2 ? length : lane == 3 ? passes : lane == 4 ? guard + exponent - z :
+                              lane == 5 ? orient : lane == 6 ? x0 : lane == 7 ? y0 : lane == 8 ? w : lane == 9 ? h : 0;
+            if (lane < kJ2kF) mine[found * kJ2kF + lane] = v;
+            ++found;
+          }
+        }
+      }
+    }
+    // the header's end: the rest of its last byte is dropped, and a last byte FF is followed by one stuffed byte
+    if (!b.dry && b.buf == 0xffu) {
+      if (b.pos >= b.end) b.dry = true;
+      else ++b.pos;
+    }
+    if (b.dry) {
+      status = 2, detail0 = r;
+      break;
+    }
+    __syncthreads();                                         // (the rows above: written a field per lane, read by every lane)
+    for (int64_t i = done; !status && i < found; ++i) {      // the packet's body: the segments in the order of their blocks
+      const int64_t* q = mine + i * kJ2kF;
+      const int64_t length = q[2];
+      const int passes = __builtin_amdgcn_readfirstlane((int)q[3]), nplanes = __builtin_amdgcn_readfirstlane((int)q[4]);
+      const int lo = __builtin_amdgcn_readfirstlane((int)length), hi = __builtin_amdgcn_readfirstlane((int)(length >> 32));
+      const int64_t seg = ((int64_t)hi << 32) | (unsigned)lo;
+      if (passes != 3 * nplanes - 2 || nplanes < 1) status = 4, detail0 = passes, detail1 = nplanes;
+      else if (nplanes > kJ2kMaxPlanes) status = 8, detail0 = nplanes;
+      else if (seg > b.end - b.pos) status = 16;
+      else {
+        if (lane == 0) mine[i * kJ2kF + 1] = b.pos;
+        b.pos += seg;
+      }
+    }
+    done = found;
+  }
+  if (status) done = 0;                                      // a flagged frame has no rows
+  __syncthreads();                                           // (a row's fields were written by other lanes than the one that fills it)
+  for (int64_t i = done + lane; i < nrows; i += PL_WAVE) mine[i * kJ2kF] = -1;
+  if (lane == 0) out[0] = status, out[1] = (int32_t)done, out[2] = detail0, out[3] = detail1;
+}
+
+#undef PL_J2K_HDR
+
 }  // namespace
+
+extern "C" int64_t pl_dicom_j2k_plan_work_bytes(int64_t n_frames, int64_t max_nodes) {
+  if (n_frames < 1 || n_frames > 65535 || max_nodes < 1 || max_nodes > (1 << 24)) return -1;
+  return n_frames * max_nodes * 16;                         // two trees a frame, a node is two int32 values
+}
+
+extern "C" int pl_dicom_j2k_plan(const unsigned char* d_bytes, int64_t nbytes, const int64_t* d_plan, const unsigned char* d_tables,
+                                 int64_t n_frames, int rows, int cols, int64_t* d_blocks, int64_t n_blocks, int32_t* d_info,
+                                 void* d_work, int64_t max_nodes, void* stream) {
+  PL_REQUIRE(d_bytes && d_plan && d_tables && d_info && d_work, "null pointer");
+  PL_REQUIRE(n_blocks == 0 || d_blocks, "null pointer");
+  PL_REQUIRE(n_frames >= 1 && n_frames <= 65535, "1 <= n_frames <= 65535");
+  PL_REQUIRE(n_blocks >= 0 && n_blocks < 2147483647, "0 <= n_blocks < 2^31");
+  PL_REQUIRE(rows >= 1 && cols >= 1 && rows <= 65535 && cols <= 65535 && nbytes >= 0, "bad shape");
+  PL_REQUIRE(max_nodes >= 1 && max_nodes <= (1 << 24), "1 <= max_nodes <= 2^24");
+  PL_REQUIRE(((uintptr_t)d_work & 15u) == 0, "d_work on a 16-byte boundary");
+  hipLaunchKernelGGL(j2k_tier2_kernel, dim3((unsigned)n_frames), dim3(PL_WAVE), 0, (hipStream_t)stream, d_bytes, nbytes, d_plan,
+                     d_tables, rows, cols, d_blocks, n_blocks, d_info, (J2kNode*)d_work, max_nodes);
+  return pl_check_launch("pl_dicom_j2k_plan");
+}
 
 extern "C" int64_t pl_dicom_j2k_work_bytes(int64_t n_frames, int rows, int cols) {
   if (n_frames < 1 || n_frames > 65535 || rows < 1 || cols < 1 || rows > 65535 || cols > 65535) return -1;

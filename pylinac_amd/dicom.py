@@ -32,12 +32,14 @@ With ``jpeg2000=True`` the same three take lossless JPEG 2000 files (1.2.840.100
 .91: T.800, one component, one tile, one layer, the 5/3 transform, code-block style 0): the host reads every frame's main
 header and packet headers (``_j2k_codestream``: tier 2), the payloads go to the device compressed and ``pl_dicom_j2k_decode``
 (``decode_jpeg2000_frames``: one wave per code block, then the inverse transform) writes the same native buffer.  Without
-the keyword they are refused as before, and ``load_zip`` refuses them always.
+the keyword they are refused as before.
 
 ``load_zip(encapsulated=True)`` reads RLE Lossless and JPEG Lossless files out of ZIP archives: the members are inflated on the
 device, where
 ``pl_dicom_encap_index`` (``index_encapsulated``) walks their items and hands the host every fragment's place and first bytes, and
-``pl_copy_ranges`` (``copy_ranges``) lays the fragments of a JPEG frame that spans several end to end.
+``pl_copy_ranges`` (``copy_ranges``) lays the fragments of a JPEG frame that spans several end to end.  With ``jpeg2000=True``
+as well it reads JPEG 2000 members: the host reads the main header from the fragment's head, ``pl_dicom_j2k_plan``
+(``plan_jpeg2000_blocks``: tier 2 on the device, one wave per frame) reads the packet headers where the member lies.
 """
 from __future__ import annotations
 
@@ -262,8 +264,8 @@ def _walk_part10(buf: memoryview, size: int | None = None, jpeg_lossless: bool =
     ``load_zip`` uses: ``buf`` holds the first bytes of a file of ``size`` bytes, the walk stops at the Pixel Data element
     header -- (offset, length) of its value are validated against ``size``, not against the prefix -- and raises
     ``_PrefixTooShort`` when the prefix ends before it (an element that is cut off is never read).  ``encapsulated`` (the
-    prefix form only): a Pixel Data element of undefined length in an RLE Lossless or a JPEG Lossless file ends the walk too,
-    ``PixelData`` = (offset of its first item, -1); the items are walked on the device."""
+    prefix form only): a Pixel Data element of undefined length in an RLE Lossless or a JPEG Lossless file (with ``jpeg2000``
+    a JPEG 2000 file) ends the walk too, ``PixelData`` = (offset of its first item, -1); the items are walked on the device."""
     n = len(buf)
     whole = size is None or n >= size
     try:
@@ -299,7 +301,7 @@ def _walk_elements(buf: memoryview, n: int, size, whole: bool, jpeg_lossless: bo
     # the syntaxes whose frames may span fragments, each behind its keyword: JPEG Lossless and JPEG 2000 are walked alike
     spanning = size is None and ((jpeg_lossless and ts in JPEG_LOSSLESS) or (jpeg2000 and ts in JPEG_2000))
     fragments = [] if ts == RLE_LOSSLESS or spanning else None
-    if items_later and (ts == RLE_LOSSLESS or ts in JPEG_LOSSLESS):
+    if items_later and (ts == RLE_LOSSLESS or ts in JPEG_LOSSLESS or (jpeg2000 and ts in JPEG_2000)):
         fragments = _HEADER_ONLY
     frame_table = [] if spanning else None
     while pos + 8 <= n:
@@ -737,6 +739,12 @@ def decode_jpeg2000_frames(file_bytes, blocks, params, rows: int, cols: int, bit
 
 _J2K = "JPEG 2000 Pixel Data: "
 _J2K_TRUNCATED = "not a lossless JPEG 2000 stream: truncated code block"
+# (one text each for what the host's packet parse and the device's, ``plan_jpeg2000_blocks``, both find)
+_J2K_HEADER_SHORT = "the packet header of resolution {} runs out of bytes"
+_J2K_PASSES = "({} coding passes for {} magnitude bit planes)"
+_J2K_PLANES = "a code block of {} magnitude bit planes: at most {}"
+_J2K_BEYOND = "(its segment reaches beyond the tile-part)"
+_J2K_SECOND_SOT = "a second SOT: more than one tile-part"
 _J2K_REFUSED = {0xFF53: "COC (coding style of a component)", 0xFF5D: "QCC (quantisation of a component)",
                 0xFF5E: "RGN (region of interest)", 0xFF5F: "POC (progression order change)", 0xFF60: "PPM (packed packet headers)",
                 0xFF61: "PPT (packed packet headers)", 0xFF50: "CAP (extended capabilities)", 0xFF59: "CPF (corresponding profile)"}
@@ -823,27 +831,41 @@ def _j2k_passes(bio: _J2kBits) -> int:
     return 6 + v if v < 31 else 37 + bio.bits(7)
 
 
-def _j2k_main_header(mv, n: int, rows: int, cols: int, bits: int, name: str):
+def _j2k_main_header(mv, n: int, rows: int, cols: int, bits: int, name: str, total: int | None = None):
     """SOC, then the marker segments up to SOT (T.800 Annex A) -> (position of SOT, levels, precision, signed, guard bits,
     exponents per subband, (xcb, ycb), precinct exponents per resolution or None); what the main header shows of a stream this
-    path does not decode is refused here, naming the marker or the field."""
+    path does not decode is refused here, naming the marker or the field.  ``total`` (``load_zip``): ``mv`` holds the first
+    ``n`` bytes of a stream of ``total`` bytes; ``_PrefixTooShort`` when they end inside the header where the stream does
+    not."""
     def u16(at):
         return (mv[at] << 8) | mv[at + 1]
 
     def u32(at):
         return (u16(at) << 16) | u16(at + 2)
 
+    if total is None:
+        total = n
+
+    def need(upto):                                         # bytes [0, upto) are looked at next
+        if n < upto <= total:
+            raise _PrefixTooShort
+
+    need(12)
     if n >= 12 and bytes(mv[4:8]) == b"jP  ":
         raise NotImplementedError(f"{name}: {_J2K}a JP2 file (box wrapper) where DICOM encapsulates the raw codestream")
+    need(2)
     if n < 2 or u16(0) != 0xFF4F:
         raise ValueError(f"{name}: {_J2K}the codestream does not start with SOC (FF4F)")
     pos, siz, cod, qcd = 2, None, None, None
     while True:
+        need(pos + 4)
         if pos + 4 > n:
             raise ValueError(f"{name}: {_J2K}the main header ends without SOT")
         marker, ln = u16(pos), u16(pos + 2)
         if marker >> 8 != 0xFF:
             raise ValueError(f"{name}: {_J2K}a marker was expected at byte {pos} of the frame")
+        if ln >= 2:
+            need(pos + 2 + ln)
         if ln < 2 or pos + 2 + ln > n:
             raise ValueError(f"{name}: {_J2K}the segment of marker {marker:04X} lies outside the frame (cut off)")
         if marker == 0xFF90:
@@ -910,19 +932,21 @@ def _j2k_main_header(mv, n: int, rows: int, cols: int, bits: int, name: str):
     return pos, cod[0], siz[0], siz[1], qcd[0], qcd[1], (cod[1], cod[2]), cod[3]
 
 
-def _j2k_codestream(data, rows: int, cols: int, bits: int, name: str):
-    """One frame's JPEG 2000 codestream (``data``: its bytes, a uint8 array) -> (levels, precision, signed, [(segment offset
-    inside ``data``, length, passes, magnitude bit planes, orientation, x0, y0, w, h)] per included code block).  The main
-    header (``_j2k_main_header``), SOT and SOD, then tier 2 (T.800 Annex B): one packet per resolution of the one tile -- the
-    zero-length bit, per subband the inclusion and zero-bit-plane tag trees, the passes, ``Lblock`` and the segment length of
-    every included block, the header byte-aligned -- and the packet's body, the segments in the same order.
-    ``NotImplementedError`` for what this path does not decode, ``ValueError`` for a malformed or truncated stream."""
-    mv = memoryview(np.ascontiguousarray(data, dtype=np.uint8))
-    n = len(mv)
-    sot, levels, prec, signed, guard, exps, (xcb, ycb), precincts = _j2k_main_header(mv, n, rows, cols, bits, name)
-
+def _j2k_tile_header(mv, n: int, sot: int, name: str, total: int | None = None):
+    """SOT at ``sot`` and the tile-part header through SOD -> (the first packet's position, the tile-part's end, Psot).
+    ``total``: ``_j2k_main_header``'s.  With a prefix the marker behind the tile-part (a second SOT is refused) is the
+    caller's to look at, and so are the last three bytes that place the end of a tile-part with Psot = 0: the end returned is
+    then ``total``."""
     def u16(at):
         return (mv[at] << 8) | mv[at + 1]
+
+    whole = total is None or n >= total
+    if total is None:
+        total = n
+
+    def need(upto):
+        if n < upto <= total:
+            raise _PrefixTooShort
 
     if u16(sot + 2) != 10:
         raise ValueError(f"{name}: {_J2K}malformed SOT segment")
@@ -933,16 +957,19 @@ def _j2k_codestream(data, rows: int, cols: int, bits: int, name: str):
         raise NotImplementedError(f"{name}: {_J2K}SOT with TPsot = {tpsot}, TNsot = {tnsot}: more than one tile-part")
     if psot:
         end = sot + psot
-        if psot < 14 or end > n:
-            raise ValueError(f"{name}: {_J2K}SOT states a tile-part of {psot} bytes where {n - sot} are left (cut off)")
+        if psot < 14 or end > total:
+            raise ValueError(f"{name}: {_J2K}SOT states a tile-part of {psot} bytes where {total - sot} are left (cut off)")
         if end + 2 <= n and u16(end) == 0xFF90:
-            raise NotImplementedError(f"{name}: {_J2K}a second SOT: more than one tile-part")
-    else:                                                   # up to EOC (an item's pad byte may follow it)
+            raise NotImplementedError(f"{name}: {_J2K}{_J2K_SECOND_SOT}")
+    elif whole:                                             # up to EOC (an item's pad byte may follow it)
         end = n - 2 if n >= 2 and u16(n - 2) == 0xFFD9 else n - 3 if n >= 3 and u16(n - 3) == 0xFFD9 else n
+    else:
+        end = total
     pos = sot + 12
     while True:                                             # the tile-part header
         if pos + 2 > end:
             raise ValueError(f"{name}: {_J2K}the tile-part header ends without SOD")
+        need(pos + 2)
         marker = u16(pos)
         if marker == 0xFF93:
             pos += 2
@@ -952,12 +979,19 @@ def _j2k_codestream(data, rows: int, cols: int, bits: int, name: str):
             raise NotImplementedError(f"{name}: {_J2K}marker {marker:04X}, {what}, is not decoded by this path")
         if marker not in _J2K_SKIPPED:
             raise ValueError(f"{name}: {_J2K}marker {marker:04X} where the tile-part header or SOD was expected")
+        if pos + 4 <= end:
+            need(pos + 4)
         if pos + 4 > end or u16(pos + 2) < 2 or pos + 2 + u16(pos + 2) > end:
             raise ValueError(f"{name}: {_J2K}the segment of marker {marker:04X} lies outside the tile-part (cut off)")
         pos += 2 + u16(pos + 2)
-    # ---- the geometry: resolutions, subbands (the low band first along either axis), code blocks ---------------------------
+    return pos, end, psot
+
+
+def _j2k_geometry(rows: int, cols: int, levels: int, xcb: int, ycb: int, precincts, exps, name: str):
+    """The geometry the main header fixes, resolution by resolution (a generator: what it refuses of resolution r is raised
+    when r is reached) -> (r, code-block width, height, [(orientation, x0, y0, width, height, exponent)] per subband, the low
+    band first along either axis; empty bands are listed).  The host's packet parse and the plan of the device's walk it."""
     res = [((cols + (1 << d) - 1) >> d, (rows + (1 << d) - 1) >> d) for d in range(levels, -1, -1)]
-    blocks = []
     for r, (rw, rh) in enumerate(res):
         ppx, ppy = precincts[r] if precincts else (15, 15)
         if ((rw + (1 << ppx) - 1) >> ppx) > 1 or ((rh + (1 << ppy) - 1) >> ppy) > 1:
@@ -971,6 +1005,44 @@ def _j2k_codestream(data, rows: int, cols: int, bits: int, name: str):
         else:
             lw, lh = res[r - 1]
             bands = [(1, lw, 0, rw - lw, lh, exps[3 * r - 2]), (2, 0, lh, lw, rh - lh, exps[3 * r - 1]), (3, lw, lh, rw - lw, rh - lh, exps[3 * r])]
+        yield r, cbw, cbh, bands
+
+
+def _j2k_tree_nodes(w: int, h: int) -> int:
+    """the nodes of a tag tree over ``w`` x ``h`` leaves"""
+    n = w * h
+    while (w, h) != (1, 1):
+        w, h = (w + 1) // 2, (h + 1) // 2
+        n += w * h
+    return n
+
+
+def _j2k_block_counts(geometry) -> tuple[int, int]:
+    """-> (the code blocks of a frame, included or not: the rows ``plan_jpeg2000_blocks`` fills; the nodes of its largest tag
+    tree)"""
+    blocks, nodes = 0, 1
+    for _, cbw, cbh, bands in geometry:
+        for _, _, _, bw, bh, _ in bands:
+            if bw and bh:
+                ncx, ncy = (bw + cbw - 1) // cbw, (bh + cbh - 1) // cbh
+                blocks += ncx * ncy
+                nodes = max(nodes, _j2k_tree_nodes(ncx, ncy))
+    return blocks, nodes
+
+
+def _j2k_codestream(data, rows: int, cols: int, bits: int, name: str):
+    """One frame's JPEG 2000 codestream (``data``: its bytes, a uint8 array) -> (levels, precision, signed, [(segment offset
+    inside ``data``, length, passes, magnitude bit planes, orientation, x0, y0, w, h)] per included code block).  The main
+    header (``_j2k_main_header``), SOT and SOD (``_j2k_tile_header``), then tier 2 (T.800 Annex B): one packet per resolution
+    of the one tile -- the zero-length bit, per subband the inclusion and zero-bit-plane tag trees, the passes, ``Lblock`` and
+    the segment length of every included block, the header byte-aligned -- and the packet's body, the segments in the same
+    order.  ``NotImplementedError`` for what this path does not decode, ``ValueError`` for a malformed or truncated stream."""
+    mv = memoryview(np.ascontiguousarray(data, dtype=np.uint8))
+    n = len(mv)
+    sot, levels, prec, signed, guard, exps, (xcb, ycb), precincts = _j2k_main_header(mv, n, rows, cols, bits, name)
+    pos, end, _ = _j2k_tile_header(mv, n, sot, name)
+    blocks = []
+    for r, cbw, cbh, bands in _j2k_geometry(rows, cols, levels, xcb, ycb, precincts, exps, name):
         bio, found = _J2kBits(mv, pos, end), []
         try:
             if bio.bit():
@@ -994,14 +1066,14 @@ def _j2k_codestream(data, rows: int, cols: int, bits: int, name: str):
                                           min(cbw, bw - cx * cbw), min(cbh, bh - cy * cbh)))
             pos = bio.align()
         except _J2kShort:
-            raise ValueError(f"{name}: {_J2K}the packet header of resolution {r} runs out of bytes") from None
+            raise ValueError(f"{name}: {_J2K}{_J2K_HEADER_SHORT.format(r)}") from None
         for length, passes, planes, *rest in found:
             if passes != 3 * planes - 2 or planes < 1:
-                raise ValueError(f"{name}: {_J2K_TRUNCATED} ({passes} coding passes for {planes} magnitude bit planes)")
+                raise ValueError(f"{name}: {_J2K_TRUNCATED} {_J2K_PASSES.format(passes, planes)}")
             if planes > _J2K_MAX_PLANES:
-                raise NotImplementedError(f"{name}: {_J2K}a code block of {planes} magnitude bit planes: at most {_J2K_MAX_PLANES}")
+                raise NotImplementedError(f"{name}: {_J2K}{_J2K_PLANES.format(planes, _J2K_MAX_PLANES)}")
             if length > end - pos:
-                raise ValueError(f"{name}: {_J2K_TRUNCATED} (its segment reaches beyond the tile-part)")
+                raise ValueError(f"{name}: {_J2K_TRUNCATED} {_J2K_BEYOND}")
             blocks.append((pos, length, passes, planes, *rest))
             pos += length
     return levels, prec, signed, blocks
@@ -1272,15 +1344,16 @@ def _finish_frames(decode, verify, metas, owner, rows: int, cols: int, dtype, ra
     return x
 
 
-def _member_header(raw, member, what: str, encapsulated: bool = False):
+def _member_header(raw, member, what: str, encapsulated: bool = False, jpeg2000: bool = False):
     """The Part-10 header of one archive member without inflating it whole -> its metadata, or None for a member without
     ``DICM`` at byte 128.  ``raw``: the member's bytes as they lie in the archive (a uint8 array view).  A stored member is
     walked where it lies; of a deflated one the first 64 KiB are inflated on the host, and twice as many again until the walk
-    reaches the (7FE0,0010) element header or the member ends.  ``encapsulated``: ``_walk_part10``'s."""
+    reaches the (7FE0,0010) element header or the member ends.  ``encapsulated``, ``jpeg2000``: ``_walk_part10``'s."""
     import zlib
 
-    def walk(view, size):                                   # (the keyword only when set: the default call stays (view, size))
-        return _walk_part10(view, size, encapsulated=True) if encapsulated else _walk_part10(view, size)
+    def walk(view, size):                                   # (the keywords only when set: the default call stays (view, size))
+        kw = dict(encapsulated=True, **(dict(jpeg2000=True) if jpeg2000 else {})) if encapsulated else {}
+        return _walk_part10(view, size, **kw)
 
     if member.size < 132:
         return None
@@ -1306,7 +1379,8 @@ def _member_header(raw, member, what: str, encapsulated: bool = False):
 
 
 def load_zip(source, members=None, verify: bool = True, dtype=None, raw_pixels: bool = False, invert_pixels: bool | None = None,
-             correct_unused_bits: bool = False, device=None, check: bool = True, encapsulated: bool = False):
+             correct_unused_bits: bool = False, device=None, check: bool = True, encapsulated: bool = False,
+             jpeg2000: bool = False):
     """``load_frames([zf.read(n) for n in names], ...)`` for a ZIP archive of native Part-10 files (what
     ``DicomImageStack.from_zip`` / ``CatPhan504.from_zip`` are handed) without a member ever being inflated whole on the host
     -> (device tensor [N, H, W], list of per-member metadata, names).  The archive goes to the device compressed; ONE
@@ -1329,19 +1403,35 @@ def load_zip(source, members=None, verify: bool = True, dtype=None, raw_pixels: 
     whose markers run past the head has its leading bytes fetched (4 KiB, doubling).  No Pixel Data comes back to the host.
     Without the keyword such members raise ``NotImplementedError`` as they always did.
 
+    ``jpeg2000=True`` (with ``encapsulated=True``; ``ValueError`` without it) takes archives whose members are all JPEG 2000
+    (``JPEG_2000``): ``load_frames([zf.read(n) for n in names], jpeg2000=True, ...)``, the same contract again.  The host reads
+    each frame's main header, SOT and tile-part header from the heads (a main header that runs past them has the stream's
+    leading bytes fetched); the packet headers, which lie all through the stream, are read by the device
+    (``plan_jpeg2000_blocks``) where the member was inflated, and what only that walk can find -- a packet header out of
+    bytes, a truncated code block, more than 30 bit planes, a segment beyond the tile-part -- is raised from ONE transfer of
+    its result before the code blocks are decoded, whatever ``check`` says, as ``load_frames`` raises it unconditionally.
+    Two bytes per frame, the marker behind the tile-part, come back with one more transfer (a second tile-part is refused).
+    The ORDER of refusals differs from ``load_frames`` where several faults meet: what the host reads of ANY member's headers
+    and geometry is raised before what the device finds in any member (its result is read once, for all of them), so an
+    archive whose member 0 has a truncated block and whose member 1 has a COC marker names member 1 where ``load_frames``
+    names file 0; each message is the one ``load_frames`` has for that member.
+    Without the keyword JPEG 2000 members are refused as before.
+
     The device form is for archives of MANY members of moderate size -- a CT volume: 80 - 300 slices of 0.5 MB, every Deflate
     stream a wave of its own.  One Deflate stream is one serial chain (about 150 ns per output byte), so an archive of a few
     large deflated members (a Winston-Lutz session of 1280 x 1280 frames) is read faster by ``zipfile`` on the host followed by
     ``load_frames``; stored members cost a copy either way."""
     from . import zipstack
 
+    if jpeg2000 and not encapsulated:
+        raise ValueError("load_zip: jpeg2000=True extends encapsulated=True; pass both")
     archive, what, host, dbuf = zipstack.stage(source, device)
     hv = host.numpy()
     taken, metas, labels = [], [], []
     for m in zipstack._select(archive, members, what):
         name = f"{what}: member {m.name!r}"
         try:
-            meta = _member_header(hv[m.data_offset:m.data_offset + m.compressed_size], m, name, encapsulated)
+            meta = _member_header(hv[m.data_offset:m.data_offset + m.compressed_size], m, name, encapsulated, jpeg2000)
         except NotImplementedError as e:
             raise NotImplementedError(f"{name}: {e}") from None
         if meta is None:
@@ -1356,10 +1446,14 @@ def load_zip(source, members=None, verify: bool = True, dtype=None, raw_pixels: 
     kind, lay, owner, inside = _frame_plan(metas, "load_zip", "members")
     if kind == "jpegll":
         _jpegll_refusals(lay[0].sample_bytes, lay[0].cols)
+    elif kind == "j2k":
+        _j2k_refusals(lay[0].sample_bytes)
     stack = zipstack.run(taken, what, host, dbuf, verify=verify, check=check)
     copied = None
     if kind == "jpegll":
         decode, owner, copied = _zip_jpegll_decode(stack, metas, lay, labels, correct_unused_bits)
+    elif kind == "j2k":
+        decode, owner, copied = _zip_j2k_decode(stack, metas, lay, labels, correct_unused_bits, what)
     else:
         if kind == "rle":
             heads = _index_members(stack, metas, lay, labels, False)
@@ -1527,20 +1621,15 @@ def _fetch_stream_head(buffer: torch.Tensor, pieces: list, nbytes: int) -> bytes
     return (parts[0] if len(parts) == 1 else torch.cat(parts)).cpu().numpy().tobytes() if parts else b""
 
 
-def _zip_jpegll_decode(stack, metas, lay, names, correct_unused_bits: bool):
-    """The JPEG Lossless half of ``load_zip(encapsulated=True)``: every frame's markers parsed from the heads of its fragments
-    (``_jpegll_header``; leading bytes fetched from the device only when they run past the heads), a frame of one fragment
-    decoded where it lies, the frames that span fragments laid end to end at 4-byte boundaries of a staging buffer by ONE
-    ``copy_ranges`` -> (decode(out=, rescale=) for ``_finish_frames``, the member of every frame, the copy's status or
-    None).  ``decode_jpeg_lossless_frames`` takes one buffer: with both kinds of frames it is called once per buffer, into
-    the two parts of one native tensor."""
-    rows, cols, ib = lay[0].rows, lay[0].cols, lay[0].sample_bytes
-    dev, base = stack.buffer.device, stack.offsets
-    heads = _index_members(stack, metas, lay, names, True)
-    scans, staged, ranges, pos = [], [], [], 0
+def _zip_frame_headers(stack, metas, lay, names, heads, codec: str, parse):
+    """Every frame of the members of an archive whose frames may span fragments (JPEG Lossless, JPEG 2000) -> (member, the
+    frame's pieces (offset in ``stack.buffer``, length), its length, ``parse(data, name, total)``'s answer) per frame.
+    ``parse`` is given the heads of the frame's fragments as far as they are the stream's leading bytes; when it raises
+    ``_PrefixTooShort`` the leading bytes are fetched from the device (4 KiB, or twice what the heads gave, and doubling)."""
+    base = stack.offsets
     for k, (meta, l) in enumerate(zip(metas, lay)):
         index_of = {o: j for j, (o, _) in enumerate(meta.PixelDataFragments)}
-        for frags in _jpegll_frames(meta, l.frames, names[k]):
+        for frags in _jpegll_frames(meta, l.frames, names[k], codec):
             total = sum(n for _, n in frags)
             pieces = [(int(base[k]) + o, n) for o, n in frags]
             data = b""
@@ -1551,21 +1640,37 @@ def _zip_jpegll_decode(stack, metas, lay, names, correct_unused_bits: bool):
             want = max(4096, 2 * len(data))                 # (the heads of many short fragments may hold more than 4 KiB)
             while True:
                 try:
-                    header = _jpegll_header(data, rows, cols, ib * 8, names[k], total=total)
+                    parsed = parse(data, names[k], total)
                     break
                 except _PrefixTooShort:
                     data = _fetch_stream_head(stack.buffer, pieces, min(want, total))
                     want *= 2
-            staged.append(len(pieces) > 1)
-            if len(pieces) == 1:
-                scans.append((k, pieces[0][0], header))
-            else:
-                scans.append((k, pos, header))
-                at = pos
-                for o, n in pieces:
-                    ranges.append((o, n, at))
-                    at += n
-                pos += (total + 3) & ~3
+            yield k, pieces, total, parsed
+
+
+def _zip_jpegll_decode(stack, metas, lay, names, correct_unused_bits: bool):
+    """The JPEG Lossless half of ``load_zip(encapsulated=True)``: every frame's markers parsed from the heads of its fragments
+    (``_jpegll_header``; leading bytes fetched from the device only when they run past the heads), a frame of one fragment
+    decoded where it lies, the frames that span fragments laid end to end at 4-byte boundaries of a staging buffer by ONE
+    ``copy_ranges`` -> (decode(out=, rescale=) for ``_finish_frames``, the member of every frame, the copy's status or
+    None).  ``decode_jpeg_lossless_frames`` takes one buffer: with both kinds of frames it is called once per buffer, into
+    the two parts of one native tensor."""
+    rows, cols, ib = lay[0].rows, lay[0].cols, lay[0].sample_bytes
+    dev = stack.buffer.device
+    heads = _index_members(stack, metas, lay, names, True)
+    scans, staged, ranges, pos = [], [], [], 0
+    for k, pieces, total, header in _zip_frame_headers(stack, metas, lay, names, heads, "JPEG",
+                                                       lambda data, name, total: _jpegll_header(data, rows, cols, ib * 8, name, total=total)):
+        staged.append(len(pieces) > 1)
+        if len(pieces) == 1:
+            scans.append((k, pieces[0][0], header))
+        else:
+            scans.append((k, pos, header))
+            at = pos
+            for o, n in pieces:
+                ranges.append((o, n, at))
+                at += n
+            pos += (total + 3) & ~3
     tables, owner = _jpegll_tables(scans)
     staged = np.asarray(staged, dtype=bool)
     staging = copied = None
@@ -1590,6 +1695,193 @@ def _zip_jpegll_decode(stack, metas, lay, names, correct_unused_bits: bool):
             done += idx.size
         x = _from_native(native[back], torch.cat(status)[back], rows, cols, bits, common["bits_stored"], rep, correct_unused_bits,
                          out, rescale, dev)
+        return x, x._pl_status
+
+    return decode, owner, copied
+
+
+J2K_PLAN_FIELDS, J2K_PLAN_TABLE = 8, 72                     # PL_J2K_PLAN_FIELDS, PL_J2K_PLAN_TABLE
+J2K_PLAN_UNSOUND, J2K_PLAN_HEADER_SHORT, J2K_PLAN_PASSES, J2K_PLAN_PLANES, J2K_PLAN_BEYOND = 1, 2, 4, 8, 16
+
+
+def plan_jpeg2000_blocks(file_bytes, plan, tables, rows: int, cols: int, max_nodes: int, n_blocks: int | None = None, device=None,
+                         blocks: torch.Tensor | None = None):
+    """``pl_dicom_j2k_plan``, tier 2 of JPEG 2000 on the device: the packet headers of N codestreams lying anywhere inside
+    ``file_bytes`` (uint8 array / tensor; a device tensor is used in place), one wave per frame, nothing read back ->
+    (blocks int64 [n_blocks, 10] as ``decode_jpeg2000_frames`` takes them, info int32 [N, 4]), both on the device.  ``plan``
+    int64 [N, ``J2K_PLAN_FIELDS``] and ``tables`` uint8 [N, ``J2K_PLAN_TABLE``] state what the host read of each stream's
+    headers (``_j2k_plan_row`` builds a frame's pair; include/pylinac_hip.h has the layout): where the stream and its first
+    packet lie, the tile-part's end, the coding parameters, and the rows of ``blocks`` the frame owns -- one for every code
+    block of its geometry.  The rows of the included blocks are filled from the front of that range, the rest carry frame
+    -1, which the decode skips.  ``info``: status (``J2K_PLAN_UNSOUND`` the plan row is unsound, nothing else is written;
+    ``J2K_PLAN_HEADER_SHORT`` a packet header runs out of bytes; ``J2K_PLAN_PASSES`` passes that are not 3 x planes - 2;
+    ``J2K_PLAN_PLANES`` more than 30 bit planes; ``J2K_PLAN_BEYOND`` a segment beyond the tile-part), the number of included
+    blocks, two details.  A flagged frame has no rows.  ``max_nodes``: the nodes of the largest tag tree
+    (``_j2k_block_counts``); ``n_blocks``: the rows of ``blocks`` (taken from a host ``plan`` when absent); ``blocks``: an
+    int64 device tensor [n_blocks, 10] to write into."""
+    dev = on_device(device)
+    buf = bytes_tensor(file_bytes, dev)
+    nbytes, buf = int(buf.numel()), _addressable(buf)
+    if n_blocks is None:
+        if isinstance(plan, torch.Tensor):
+            raise ValueError("plan_jpeg2000_blocks: n_blocks is needed with a device plan")
+        n_blocks = int(np.max(np.asarray(plan, dtype=np.int64).reshape(-1, J2K_PLAN_FIELDS)[:, 5:7].sum(axis=1), initial=0))
+    plan_t = index_tensor(plan, torch.int64, dev).reshape(-1, J2K_PLAN_FIELDS)
+    tab = bytes_tensor(tables, dev).reshape(-1, J2K_PLAN_TABLE)
+    n = int(plan_t.shape[0])
+    if int(tab.shape[0]) != n:
+        raise ValueError("plan_jpeg2000_blocks: plan [N, 8] and tables [N, 72]")
+    lib = _lib.load()
+    nwork = int(lib.pl_dicom_j2k_plan_work_bytes(n, int(max_nodes)))
+    if nwork < 0 or not 0 <= int(n_blocks) < 2 ** 31:
+        raise ValueError(f"plan_jpeg2000_blocks: {n} frames (1 .. 65535), max_nodes = {max_nodes} (1 .. 2^24), n_blocks = {n_blocks}")
+    if blocks is None:
+        blocks = torch.empty((int(n_blocks), 10), dtype=torch.int64, device=dev)
+    elif blocks.dtype != torch.int64 or tuple(blocks.shape) != (int(n_blocks), 10) or not blocks.is_contiguous() or not blocks.is_cuda:
+        raise ValueError(f"plan_jpeg2000_blocks: blocks must be a contiguous int64 device tensor [{n_blocks}, 10]")
+    info = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    work = torch.empty(nwork, dtype=torch.uint8, device=dev)
+    check(lib.pl_dicom_j2k_plan(buf.data_ptr(), nbytes, plan_t.data_ptr(), tab.data_ptr(), n, int(rows), int(cols),
+                                blocks.data_ptr() if n_blocks else None, int(n_blocks), info.data_ptr(), work.data_ptr(),
+                                int(max_nodes), torch.cuda.current_stream(dev).cuda_stream), "pl_dicom_j2k_plan")
+    return blocks, info
+
+
+def _j2k_plan_row(start: int, length: int, first: int, end: int, levels: int, xcb: int, ycb: int, guard: int, exps, precincts,
+                  row0: int, nrows: int):
+    """one frame's row of ``plan`` and of ``tables`` for ``plan_jpeg2000_blocks``; ``end`` 0: Psot = 0"""
+    coding = levels | xcb << 8 | ycb << 16 | guard << 24 | (1 << 32 if precincts else 0)
+    table = np.zeros(J2K_PLAN_TABLE, dtype=np.uint8)
+    table[:3 * levels + 1] = exps[:3 * levels + 1]
+    if precincts:
+        table[49:49 + levels + 1] = [px | py << 4 for px, py in precincts]
+    return (start, length, first, end, coding, row0, nrows, 0), table
+
+
+def _stream_places(pieces: list, at: int, count: int) -> list:
+    """where bytes [at, at + count) of a stream lie in the buffer that holds its pieces (offset, length)"""
+    out = []
+    for off, ln in pieces:
+        if at >= ln:
+            at -= ln
+            continue
+        take = min(ln - at, count)
+        out += range(off + at, off + at + take)
+        count, at = count - take, 0
+        if not count:
+            break
+    return out
+
+
+def _check_j2k_plan(info: np.ndarray, owner, names) -> None:
+    """what only the device's walk of the packet headers finds, in ``_j2k_codestream``'s words, for the first flagged frame"""
+    for k in np.flatnonzero(info[:, 0]):
+        status, _, d0, d1 = (int(v) for v in info[k])
+        name = names[owner[k]]
+        if status & J2K_PLAN_HEADER_SHORT:
+            raise ValueError(f"{name}: {_J2K}{_J2K_HEADER_SHORT.format(d0)}")
+        if status & J2K_PLAN_PASSES:
+            raise ValueError(f"{name}: {_J2K_TRUNCATED} {_J2K_PASSES.format(d0, d1)}")
+        if status & J2K_PLAN_PLANES:
+            raise NotImplementedError(f"{name}: {_J2K}{_J2K_PLANES.format(d0, _J2K_MAX_PLANES)}")
+        if status & J2K_PLAN_BEYOND:
+            raise ValueError(f"{name}: {_J2K_TRUNCATED} {_J2K_BEYOND}")
+        raise ValueError(f"{name}, frame {k} of the stack: {_J2K}the plan of its packet headers is unsound")
+
+
+class _J2kFrame(NamedTuple):
+    """what ``_zip_j2k_decode`` keeps of a frame between its headers and its plan row"""
+    staged: bool            # it spans fragments: laid end to end in the staging buffer
+    start: int              # where its stream begins in the buffer it is planned and decoded in
+    length: int
+    first: int              # the first packet's offset inside the stream
+    end: int                # the tile-part's end inside the stream, 0 for Psot = 0
+    coding: tuple           # levels, xcb, ycb, guard bits, exponents, precincts
+    nrows: int              # the code blocks of its geometry
+    nodes: int              # the nodes of its largest tag tree
+    params: tuple           # its row of ``decode_jpeg2000_frames``' params
+
+
+def _zip_j2k_decode(stack, metas, lay, names, correct_unused_bits: bool, what: str):
+    """The JPEG 2000 half of ``load_zip(encapsulated=True, jpeg2000=True)``, as ``_zip_jpegll_decode``: every frame's main
+    header, SOT and tile-part header parsed from the heads of its fragments (leading bytes fetched from the device only when
+    the headers run past them), a frame of one fragment planned and decoded where it lies, the frames that span fragments
+    laid end to end at 4-byte boundaries of a staging buffer by ONE ``copy_ranges``; per buffer one ``plan_jpeg2000_blocks``
+    and one ``decode_jpeg2000_frames`` -> (decode(out=, rescale=) for ``_finish_frames``, the member of every frame, the
+    copy's status or None).  The plan's result is read once, here, and what it flags is raised before any block is
+    decoded.  An archive with frames that span fragments pays one transfer more: the copy's status is read before the plan
+    call, which reads what was copied."""
+    rows, cols, ib = lay[0].rows, lay[0].cols, lay[0].sample_bytes
+    dev = stack.buffer.device
+    heads = _index_members(stack, metas, lay, names, True)
+    frames, owner, ranges, peeks, pos = [], [], [], [], 0
+
+    def parse(data, name, total):
+        mv = memoryview(data)
+        main = _j2k_main_header(mv, len(mv), rows, cols, ib * 8, name, total=total)
+        return main, _j2k_tile_header(mv, len(mv), main[0], name, total=total), len(mv)
+
+    for k, pieces, total, (main, (first, end, psot), seen) in _zip_frame_headers(stack, metas, lay, names, heads, "JPEG 2000", parse):
+        _, levels, prec, signed, guard, exps, (xcb, ycb), precincts = main
+        nrows, nodes = _j2k_block_counts(_j2k_geometry(rows, cols, levels, xcb, ycb, precincts, exps, names[k]))
+        if psot and seen < end + 2 <= total:                # the marker behind the tile-part is not in hand
+            peeks.append((k, _stream_places(pieces, end, 2)))
+        staged = len(pieces) > 1
+        frames.append(_J2kFrame(staged, pos if staged else pieces[0][0], total, first, end if psot else 0,
+                                (levels, xcb, ycb, guard, exps, precincts), nrows, nodes, (levels, prec, signed, 0)))
+        owner.append(k)
+        if staged:
+            at = pos
+            for o, n in pieces:
+                ranges.append((o, n, at))
+                at += n
+            pos += (total + 3) & ~3
+    if peeks:                                               # one transfer: two bytes per frame
+        places = torch.from_numpy(np.asarray([p for _, where in peeks for p in where], dtype=np.int64)).to(dev)
+        behind = stack.buffer[places].cpu().numpy().reshape(-1, 2)
+        for (k, _), pair in zip(peeks, behind):
+            if tuple(pair) == (0xFF, 0x90):
+                raise NotImplementedError(f"{names[k]}: {_J2K}{_J2K_SECOND_SOT}")
+    staging = copied = None
+    if ranges:
+        moves = np.asarray(ranges, dtype=np.int64)
+        staging = torch.empty(max(pos, 16), dtype=torch.uint8, device=dev)
+        copied = copy_ranges(stack.buffer, staging, moves[:, 0], moves[:, 1], moves[:, 2], device=dev)
+        if bool(copied.any()):                              # (the plan below reads what was copied)
+            raise ValueError(f"{what}: a fragment of a frame that spans fragments lies outside the extracted members")
+    is_staged = np.asarray([f.staged for f in frames], dtype=bool)
+    groups = []
+    for buf, sel in ((stack.buffer, ~is_staged), (staging, is_staged)):
+        idx = np.flatnonzero(sel)
+        if not idx.size:
+            continue
+        plan, tables, row0 = [], [], 0
+        for f in (frames[j] for j in idx):
+            row, table = _j2k_plan_row(f.start, f.length, f.first, f.end, *f.coding, row0, f.nrows)
+            plan.append(row)
+            tables.append(table)
+            row0 += f.nrows
+        blocks, info = plan_jpeg2000_blocks(buf, np.asarray(plan, dtype=np.int64), np.stack(tables), rows, cols,
+                                            max(frames[j].nodes for j in idx), n_blocks=row0, device=dev)
+        params = np.asarray([frames[j].params for j in idx], dtype=np.int32)
+        groups.append((buf, idx, blocks, info, params))
+    order = np.concatenate([g[1] for g in groups])
+    info = (groups[0][3] if len(groups) == 1 else torch.cat([g[3] for g in groups])).cpu().numpy()
+    _check_j2k_plan(info[np.argsort(order)], owner, names)
+    common = _decode_keywords(lay[0], metas[0], correct_unused_bits, dev)
+    bits, rep = common["bits_allocated"], common["pixel_representation"]
+    back = torch.from_numpy(np.argsort(order)).to(dev)
+
+    def decode(out="container", rescale=None):              # one call per buffer, then the frames back into their order
+        native = torch.empty((len(owner), rows * cols * ib), dtype=torch.uint8, device=dev)
+        status, done = [], 0
+        for buf, idx, blocks, _, params in groups:
+            part = decode_jpeg2000_frames(buf, blocks, params, rows, cols, bits, device=dev, native=native[done:done + idx.size])
+            status.append(part._pl_status)
+            done += idx.size
+        if len(groups) > 1:
+            native, status = native[back], [torch.cat(status)[back]]
+        x = _from_native(native, status[0], rows, cols, bits, common["bits_stored"], rep, correct_unused_bits, out, rescale, dev)
         return x, x._pl_status
 
     return decode, owner, copied
