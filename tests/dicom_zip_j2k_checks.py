@@ -6,7 +6,9 @@ The reference of the plan kernel is the host's packet-header parse, ``dicom._j2k
 rows the kernel writes at the front of a frame's range are the host's list, row for row, shifted by the stream's place in the
 buffer.  The reference of the loader is ``load_frames(..., jpeg2000=True)`` on the bytes ``zipfile`` extracts -- the same
 tensor, metadata and exception, the member named where ``load_frames`` says ``file K`` -- and the source frames.  The streams
-are Pillow's (tests/dicom_j2k_checks.py), the archives tests/zip_checks.py's.  Without the feature the loader checks fail
+are Pillow's (tests/dicom_j2k_checks.py), the archives tests/zip_checks.py's.  What Pillow's encoder never writes -- status 8
+(more than 30 bit planes), a header that ends in FF, empty bands, blocks excluded between included ones -- comes from the
+test-side writer in tests/dicom_j2k_conformance_checks.py.  Without the feature the loader checks fail
 (``load_zip`` has no ``jpeg2000`` keyword) and so do the plan checks (the library has no such symbol)."""
 from __future__ import annotations
 
